@@ -10,14 +10,18 @@ in HBM: CNN -> 3x BiLSTM -> FC -> greedy CTC -> SparseTensor on device, decoded 
 the host, per-read regroup + glue overlap-consensus vote on the host.  Three batches are kept in
 flight (three engine slots / HIP streams; --slots).
 
-Timed region: --steps K steps take ~11 ms each, so K = 20 would be a quarter of a second -- too short for the
-clocks to settle or for a utilisation sampler with a 5 s period to see the GPU busy.  The region therefore runs the K
-steps --rounds R times back to back (default 45: 900 steps, ~10 s), all inside ONE barrier + synchronize bracket;
-ms_per_step = time / (K * R), value = windows of all K * R steps / time, and the line reports steps = K, rounds = R,
-timed_steps = K * R.  Nothing is skipped or cached between rounds: every step is a full submit / collect.
+Timed region: --steps K steps (~11 ms each) inside ONE barrier + synchronize bracket; ms_per_step = time / K, value = windows of
+all K steps / time.  --rounds R (default 1) repeats the K steps R times inside the same bracket (then timed_steps = K * R): a
+utilisation sampler with a 5 s period needs ~500 steps to see the GPU busy.  Nothing is skipped or cached between rounds: every step
+is a full submit / collect.  --dump-outputs DIR writes what the last timed step returned (the decoded SparseTensor, log_prob,
+prob_logits and the per-read vote matrices) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared array by array.
+
+A plain run does only that: set up, warm up, time the steps, dump, print the line.  Everything else -- the host-inclusive and
+decode-density regions, the per-kernel profiling pass with the roofline (and its rocprofv3 --pmc child runs), the CPU baseline,
+the fp16 / fp16-w2 / fp32-split configurations -- runs with --full only.
 
 `value` is measured with the batch's signal already resident in HBM (the contract of this benchmark).  What the drop-in
-boundary really receives are HOST buffers, so a second region of the same kind (`extra.host_inclusive`, --host-rounds) feeds
+boundary really receives are HOST buffers, so under --full a second region of the same kind (`extra.host_inclusive`, --host-rounds) feeds
 numpy arrays: every step cuts its 1100 windows out of a raw signal on the host (signal_io.window_signal, chiron_input.py:253-292),
 rounds the lengths (chiron_eval.py:337) and hands host pointers to chiron_engine_submit, which stages them in pinned memory and
 copies them over PCIe inside the step.
@@ -93,7 +97,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rounds", type=int, default=45, help="the timed region is --steps steps repeated this many times (one bracket)")
+    ap.add_argument("--rounds", type=int, default=1, help="the timed region is --steps steps repeated this many times (one bracket)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: host-inclusive and decode-density regions, "
+                    "per-kernel profiling pass + roofline (with rocprofv3 --pmc child runs), CPU baseline, fp16 / fp16-w2 / fp32-split configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned as "
+                    "DIR/<name>.npy (float32 / float64; rank 0)")
     ap.add_argument("--host-rounds", type=int, default=10, help="rounds of the host-inclusive region (windowing + PCIe inside the step); 0 = skip")
     ap.add_argument("--slots", type=int, default=3, help="batches in flight (engine slots / HIP streams)")
     ap.add_argument("--density-rounds", type=int, default=15, help="rounds of the realistic-decode-density region (a head fitted to emit "
@@ -116,6 +124,8 @@ def main():
                          "gloo: there is no RCCL without a GPU).  Never a measurement: the "
                          "line says data = 'stub'.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pmc_child:
         return pmc_child(args.pmc_child)
     stub = args.stub_engine > 0
@@ -188,11 +198,15 @@ def main():
         cuts = np.flatnonzero(np.diff(read_of_row[i])) + 1
         run_bounds.append(np.concatenate([[0], cuts, [BATCH]]))
 
-    def consume(res, which):
+    collected = {}      # slot -> (DecodeResult, vote matrices of its per-read runs) of the slot's latest collect (--dump-outputs)
+
+    def consume(res, which, slot):
         """host side of a step: ragged split of the SparseTensor, then the glue overlap-consensus vote
         (chiron_assemble) for every per-read run of rows in the batch"""
         idx, val = res.decoded.indices, res.decoded.values
         decoded_bases[0] += int(val.shape[0])
+        votes = []
+        collected[slot] = (res, votes)
         if not val.shape[0]:
             return
         counts = np.bincount(idx[:, 0], minlength=BATCH)
@@ -208,6 +222,7 @@ def main():
             off = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)
             cons = assembly.assemble_native(seg, off, None, "glue")
             consensus_bases[0] += int(cons[0].shape[1])
+            votes.append(cons[0])
 
     def step(i, pending, eng=eng):
         """collect the slot's finished batch, hand the slot its next batch at once, THEN do the host side of the finished one
@@ -217,12 +232,12 @@ def main():
         eng.submit(slot, x_dev[i % n_distinct], s_dev[i % n_distinct], beam_width=0, want_prob=True)
         pending[slot] = i % n_distinct
         if res is not None:
-            consume(res, which)
+            consume(res, which, slot)
 
     def drain(pending, eng=eng):
         for slot in range(args.slots):
             if pending[slot] is not None:
-                consume(eng.collect(slot), pending[slot])
+                consume(eng.collect(slot), pending[slot], slot)
                 pending[slot] = None
 
     pending = [None] * args.slots
@@ -257,10 +272,12 @@ def main():
     kbases = windows * BASES_PER_WINDOW / 1000.0
     value = kbases / dt
     decoded_total, consensus_total = decoded_bases[0], consensus_bases[0]     # the headline region's counts (consume() keeps counting)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *collected[(timed_steps - 1) % args.slots])
 
     # ---- the same steps fed from the HOST: windowing of the raw signal, length rounding and the H2D copy inside the step
     host_inclusive = None
-    if args.host_rounds > 0:
+    if args.full and args.host_rounds > 0:
         from chiron_amd import signal_io
         raw = [np.ascontiguousarray(np.concatenate([xb[i][:, :JUMP].reshape(-1), xb[i][-1, JUMP:]])) for i in range(n_distinct)]
 
@@ -272,7 +289,7 @@ def main():
             eng.submit(slot, ev[:BATCH], sl, beam_width=0, want_prob=True)
             pending[slot] = i % n_distinct
             if res is not None:
-                consume(res, which)
+                consume(res, which, slot)
 
         for i in range(args.warmup):
             host_step(i, pending)
@@ -316,80 +333,10 @@ def main():
                "roofline": None, "cpu_baseline": None,
                "extra": {"windows_per_s": round(windows / dt, 1), "decoded_bases_total": decoded_total, "host_inclusive": host_inclusive}}
     elif rank == 0:
-        # ---- per-kernel timing with HIP events on the engine's own stream (separate, untimed pass)
-        eng.profile(True)
-        for i in range(3):
-            eng.submit(0, x_dev[i % n_distinct], s_dev[i % n_distinct], beam_width=0, want_prob=True)
-            eng.collect(0)
-        stats = eng.profile_read()
-        eng.profile(False)
-        per_kernel = {k: {"avg_ms": s["total_ms"] / s["launches"], "launches_per_batch": s["launches"] / 3.0,
-                          "tflops": (s["flops"] / (s["total_ms"] * 1e-3) / 1e12) if s["total_ms"] > 0 else 0.0,
-                          "gbps": (s["bytes"] / (s["total_ms"] * 1e-3) / 1e9) if s["total_ms"] > 0 else 0.0}
-                      for k, s in stats.items()}
-        # dominant kernel = the MFMA-bound bucket (= one kernel symbol) with the largest device time in this pass
-        mfma_buckets = [k for k in BUCKET_SYMBOL if k in stats and stats[k]["total_ms"] > 0]
-        dom_key = max(mfma_buckets, key=lambda k: stats[k]["total_ms"])
-        dom = stats[dom_key]
-        dom_symbol = BUCKET_SYMBOL[dom_key]
-        achieved = dom["flops"] / (dom["total_ms"] * 1e-3) / 1e12
-        traffic, traffic_src = pmc_traffic(dom_symbol)          # the committed record (also feeds the per-kernel pmc blocks below)
-        live = None if (args.no_live_pmc or world != 1) else live_pmc_traffic()
-        if live and live.get("kernels"):
-            rec = next((v for k, v in live["kernels"].items() if dom_symbol in k), None)
-            if rec and rec.get("hbm_bytes"):
-                static_traffic, static_src = traffic, traffic_src
-                traffic = rec["hbm_bytes"]
-                traffic_src = ("measured in THIS run: child processes of this script under rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE "
-                               "(separate passes, %d / %d launches, three single-slot batches each; two more passes take the SQ counters of "
-                               "traffic_live.mfma_busy); committed record for comparison: %s (%s)"
-                               % (rec["launches_fetch"], rec["launches_write"], static_traffic, static_src))
-        per_bucket = {k: {"symbol": BUCKET_SYMBOL[k], "ms_per_batch": round(stats[k]["total_ms"] / 3.0, 4),
-                          "launches_per_batch": stats[k]["launches"] / 3.0,
-                          "achieved": round(EXECUTED_SHARE.get(k, 1.0) * stats[k]["flops"] / (stats[k]["total_ms"] * 1e-3) / 1e12, 2),
-                          "frac": round(EXECUTED_SHARE.get(k, 1.0) * stats[k]["flops"] / (stats[k]["total_ms"] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
-                          "op_equivalent_tflops": round(stats[k]["flops"] / (stats[k]["total_ms"] * 1e-3) / 1e12, 2)}
-                      for k in mfma_buckets}
-        roofline = {"kernel": dom_symbol, "bucket": dom_key, "bound": "mfma",
-                    "achieved": round(achieved, 2), "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 4), "traffic": traffic,
-                    "traffic_unit": "HBM bytes per launch, (2*FETCH_SIZE + WRITE_SIZE)*1024 of a separate rocprofv3 --pmc pass",
-                    # a kernel that does not fill the chip by construction: the wide recurrence launches one 8-wave workgroup per
-                    # 16-row group and direction; the other CUs run the other batches' kernels meanwhile (three in flight)
-                    "workgroups": (2 * ((BATCH + 15) // 16)) if dom_key == "lstm_recurrence" and _REC_FORM != "0" else None,
-                    "frac_of_the_cus_it_occupies": (round(achieved / PEAK_F32_MFMA_TFLOPS * 256.0 / min(256, 2 * ((BATCH + 15) // 16)), 4)
-                                                    if dom_key == "lstm_recurrence" and _REC_FORM != "0" else None),
-                    "algorithmic_bytes_per_launch": dom["bytes"] / dom["launches"],
-                    "avg_launch_ms": round(dom["total_ms"] / dom["launches"], 4),
-                    "flops_per_launch": dom["flops"] / dom["launches"],
-                    "flops_note": "achieved/frac count the MFMA FLOPs a kernel issues; conv_wino (Winograd F(4,3)) issues 1/2 of "
-                                  "its op's 2*3*C*C per position, op_equivalent_tflops is the op's own count over the same time",
-                    # the north-star figure -- LSTM-GEMM FLOPs of all windows / whole-job time / fp32 MFMA peak
-                    "lstm_gemm_roofline_frac_whole_path": round(windows / dt * LSTM_GEMM_FLOP_PER_WINDOW / 1e12 / PEAK_F32_MFMA_TFLOPS / world, 4),
-                    "lstm_gemm_flop_per_window": LSTM_GEMM_FLOP_PER_WINDOW,
-                    "mfma_kernels": per_bucket,
-                    "traffic_source": traffic_src,
-                    "traffic_live": None if not live else {"error": live.get("error"), "seconds": live.get("seconds"),
-                                                            "hbm_bytes_per_launch": {k: v.get("hbm_bytes") for k, v in (live.get("kernels") or {}).items()},
-                                                            # the matrix pipe in THIS run (same child passes, SQ counters): busy share of the CUs a kernel
-                                                            # holds / of the whole chip, VALU share next to it (committed record: roofline.pmc)
-                                                            "mfma_busy": {k: {f: v[f] for f in ("mfma_busy_frac", "mfma_busy_frac_of_busy_cus", "valu_busy_frac_of_busy_cus") if f in v}
-                                                                          for k, v in (live.get("kernels") or {}).items() if "mfma_busy_frac_of_busy_cus" in v}}}
-        # north_star: "rocprof HBM GB/s on the conv and MFMA utilisation on the LSTM": the PMC pass's counters next to this
-        # run's launch times (HBM GB/s = PMC bytes per launch / HIP-event launch time); absent when the PMC record is stale
-        for k in mfma_buckets:
-            pc = pmc_counters(BUCKET_SYMBOL[k])
-            if pc is not None:
-                per_bucket[k]["pmc"] = pc
-                if pc["hbm_bytes_per_launch"]:
-                    per_bucket[k]["hbm_gbps_pmc"] = round(pc["hbm_bytes_per_launch"] / (stats[k]["total_ms"] / stats[k]["launches"] * 1e-3) / 1e9, 1)
-        roofline["pmc"] = pmc_counters(dom_symbol)
-        fam = [s for k, s in stats.items() if k.startswith("conv") or k.startswith("lstm_proj")]
-        gemm_family = {"launches_per_batch": sum(s["launches"] for s in fam) / 3.0,
-                       "tflops": round(sum(s["flops"] for s in fam) / (sum(s["total_ms"] for s in fam) * 1e-3) / 1e12, 2),
-                       "ms_per_batch": round(sum(s["total_ms"] for s in fam) / 3.0, 3)}
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:   # reported baseline: rank 0 at N = 1 only
+        roofline = gemm_family = per_kernel = cpu = None
+        if args.full:
+            roofline, gemm_family, per_kernel = kernel_roofline(args, eng, x_dev, s_dev, n_distinct, windows, dt, world)
+        if args.full and not args.no_cpu_baseline and world == 1:   # reported baseline: rank 0 at N = 1 only
             cpu = cpu_baseline(spec, weights, xb, lb, eng.ratio, args.cpu_windows)
         out = {
             "metric": "kilobases/sec basecalled (DNA_default seg_len=400 batch=1100)",
@@ -413,11 +360,11 @@ def main():
                       "model_tflops_reference_op_count": round(windows / dt * MODEL_FLOP_PER_WINDOW / 1e12, 2),
                       "host_inclusive": host_inclusive, "realistic_density": None,
                       "gemm_family": gemm_family, "kernels": per_kernel}}
-    if args.density_rounds > 0 and world == 1 and rank == 0 and not stub:
+    if args.full and args.density_rounds > 0 and world == 1 and rank == 0 and not stub:
         out["extra"]["realistic_density"] = density_region(args, spec, local_rank, x_dev, s_dev, xb, lb, step, drain, decoded_bases,
                                                            consensus_bases, value)
     ref32 = None
-    if rank == 0 and world == 1 and not args.no_f16:
+    if args.full and rank == 0 and world == 1 and not args.no_f16:
         ref32 = eng.infer(x_dev[0], s_dev[0], want_logits=True)
     eng.close()
     if ref32 is not None:
@@ -438,6 +385,83 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out))
+
+
+def kernel_roofline(args, eng, x_dev, s_dev, n_distinct, windows, dt, world):
+    """--full: per-kernel timing with HIP events on the engine's own stream in a separate, untimed single-slot pass, the roofline of
+    the dominant kernel (with the live rocprofv3 --pmc child passes) -> (roofline, gemm_family, per_kernel)"""
+    eng.profile(True)
+    for i in range(3):
+        eng.submit(0, x_dev[i % n_distinct], s_dev[i % n_distinct], beam_width=0, want_prob=True)
+        eng.collect(0)
+    stats = eng.profile_read()
+    eng.profile(False)
+    per_kernel = {k: {"avg_ms": s["total_ms"] / s["launches"], "launches_per_batch": s["launches"] / 3.0,
+                      "tflops": (s["flops"] / (s["total_ms"] * 1e-3) / 1e12) if s["total_ms"] > 0 else 0.0,
+                      "gbps": (s["bytes"] / (s["total_ms"] * 1e-3) / 1e9) if s["total_ms"] > 0 else 0.0}
+                  for k, s in stats.items()}
+    # dominant kernel = the MFMA-bound bucket (= one kernel symbol) with the largest device time in this pass
+    mfma_buckets = [k for k in BUCKET_SYMBOL if k in stats and stats[k]["total_ms"] > 0]
+    dom_key = max(mfma_buckets, key=lambda k: stats[k]["total_ms"])
+    dom = stats[dom_key]
+    dom_symbol = BUCKET_SYMBOL[dom_key]
+    achieved = dom["flops"] / (dom["total_ms"] * 1e-3) / 1e12
+    traffic, traffic_src = pmc_traffic(dom_symbol)          # the committed record (also feeds the per-kernel pmc blocks below)
+    live = None if (args.no_live_pmc or world != 1) else live_pmc_traffic()
+    if live and live.get("kernels"):
+        rec = next((v for k, v in live["kernels"].items() if dom_symbol in k), None)
+        if rec and rec.get("hbm_bytes"):
+            static_traffic, static_src = traffic, traffic_src
+            traffic = rec["hbm_bytes"]
+            traffic_src = ("measured in THIS run: child processes of this script under rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE "
+                           "(separate passes, %d / %d launches, three single-slot batches each; two more passes take the SQ counters of "
+                           "traffic_live.mfma_busy); committed record for comparison: %s (%s)"
+                           % (rec["launches_fetch"], rec["launches_write"], static_traffic, static_src))
+    per_bucket = {k: {"symbol": BUCKET_SYMBOL[k], "ms_per_batch": round(stats[k]["total_ms"] / 3.0, 4),
+                      "launches_per_batch": stats[k]["launches"] / 3.0,
+                      "achieved": round(EXECUTED_SHARE.get(k, 1.0) * stats[k]["flops"] / (stats[k]["total_ms"] * 1e-3) / 1e12, 2),
+                      "frac": round(EXECUTED_SHARE.get(k, 1.0) * stats[k]["flops"] / (stats[k]["total_ms"] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
+                      "op_equivalent_tflops": round(stats[k]["flops"] / (stats[k]["total_ms"] * 1e-3) / 1e12, 2)}
+                  for k in mfma_buckets}
+    roofline = {"kernel": dom_symbol, "bucket": dom_key, "bound": "mfma",
+                "achieved": round(achieved, 2), "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(achieved / PEAK_F32_MFMA_TFLOPS, 4), "traffic": traffic,
+                "traffic_unit": "HBM bytes per launch, (2*FETCH_SIZE + WRITE_SIZE)*1024 of a separate rocprofv3 --pmc pass",
+                # a kernel that does not fill the chip by construction: the wide recurrence launches one 8-wave workgroup per
+                # 16-row group and direction; the other CUs run the other batches' kernels meanwhile (three in flight)
+                "workgroups": (2 * ((BATCH + 15) // 16)) if dom_key == "lstm_recurrence" and _REC_FORM != "0" else None,
+                "frac_of_the_cus_it_occupies": (round(achieved / PEAK_F32_MFMA_TFLOPS * 256.0 / min(256, 2 * ((BATCH + 15) // 16)), 4)
+                                                if dom_key == "lstm_recurrence" and _REC_FORM != "0" else None),
+                "algorithmic_bytes_per_launch": dom["bytes"] / dom["launches"],
+                "avg_launch_ms": round(dom["total_ms"] / dom["launches"], 4),
+                "flops_per_launch": dom["flops"] / dom["launches"],
+                "flops_note": "achieved/frac count the MFMA FLOPs a kernel issues; conv_wino (Winograd F(4,3)) issues 1/2 of "
+                              "its op's 2*3*C*C per position, op_equivalent_tflops is the op's own count over the same time",
+                # SURVEY 8(d): the north-star figure -- LSTM-GEMM FLOPs of all windows / whole-job time / fp32 MFMA peak
+                "lstm_gemm_roofline_frac_whole_path": round(windows / dt * LSTM_GEMM_FLOP_PER_WINDOW / 1e12 / PEAK_F32_MFMA_TFLOPS / world, 4),
+                "lstm_gemm_flop_per_window": LSTM_GEMM_FLOP_PER_WINDOW,
+                "mfma_kernels": per_bucket,
+                "traffic_source": traffic_src,
+                "traffic_live": None if not live else {"error": live.get("error"), "seconds": live.get("seconds"),
+                                                        "hbm_bytes_per_launch": {k: v.get("hbm_bytes") for k, v in (live.get("kernels") or {}).items()},
+                                                        # the matrix pipe in THIS run (same child passes, SQ counters): busy share of the CUs a kernel
+                                                        # holds / of the whole chip, VALU share next to it (committed record: roofline.pmc)
+                                                        "mfma_busy": {k: {f: v[f] for f in ("mfma_busy_frac", "mfma_busy_frac_of_busy_cus", "valu_busy_frac_of_busy_cus") if f in v}
+                                                                      for k, v in (live.get("kernels") or {}).items() if "mfma_busy_frac_of_busy_cus" in v}}}
+    # north_star: "rocprof HBM GB/s on the conv and MFMA utilisation on the LSTM": the PMC pass's counters next to this
+    # run's launch times (HBM GB/s = PMC bytes per launch / HIP-event launch time); absent when the PMC record is stale
+    for k in mfma_buckets:
+        pc = pmc_counters(BUCKET_SYMBOL[k])
+        if pc is not None:
+            per_bucket[k]["pmc"] = pc
+            if pc["hbm_bytes_per_launch"]:
+                per_bucket[k]["hbm_gbps_pmc"] = round(pc["hbm_bytes_per_launch"] / (stats[k]["total_ms"] / stats[k]["launches"] * 1e-3) / 1e9, 1)
+    roofline["pmc"] = pmc_counters(dom_symbol)
+    fam = [s for k, s in stats.items() if k.startswith("conv") or k.startswith("lstm_proj")]
+    gemm_family = {"launches_per_batch": sum(s["launches"] for s in fam) / 3.0,
+                   "tflops": round(sum(s["flops"] for s in fam) / (sum(s["total_ms"] for s in fam) * 1e-3) / 1e12, 2),
+                   "ms_per_batch": round(sum(s["total_ms"] for s in fam) / 3.0, 3)}
+    return roofline, gemm_family, per_kernel
 
 
 def density_region(args, spec, device_id, x_dev, s_dev, xb, lb, step, drain, decoded_bases, consensus_bases, value):
@@ -501,6 +525,20 @@ def density_region(args, spec, device_id, x_dev, s_dev, xb, lb, step, drain, dec
             "half_precision_engines_vs_fp32_greedy_strings": halves,
             "weights": "the headline's synthetic weights with LSTM forget biases -3 and an FC head fitted (tests/regimes.py:fit_emitting_head) on 256 "
                        "windows to emit 43.875 bases per window; same step as the headline: submit, collect (SparseTensor D2H), per-read glue vote"}
+
+
+def dump_outputs(out_dir, res, votes):
+    """--dump-outputs: what the last timed step handed its caller -- the decoded SparseTensor, log_prob and prob_logits of the batch
+    (collect()) and the glue vote matrices [4, length] of its per-read runs (concatenated along the length, consensus_lengths says where
+    one ends) -- as out_dir/<name>.npy; integers as float64 (exact), the rest as float32 / float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"decoded_indices": res.decoded.indices.astype(np.float64), "decoded_values": res.decoded.values.astype(np.float64),
+              "decoded_dense_shape": res.decoded.dense_shape.astype(np.float64),
+              "log_prob": res.log_prob.astype(np.float32), "prob_logits": res.prob_logits.astype(np.float32),
+              "consensus_votes": np.concatenate(votes, axis=1) if votes else np.zeros((4, 0), np.float64),
+              "consensus_lengths": np.asarray([v.shape[1] for v in votes], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def init_bookkeeping(dist, torch, backend, local_rank):

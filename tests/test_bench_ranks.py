@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -28,7 +29,7 @@ def test_bench_line_under_torchrun_with_a_stub_engine(world):
     env = dict(os.environ, OMP_NUM_THREADS="1", MKL_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", str(steps),
-           "--rounds", str(rounds), "--host-rounds", "1", "--warmup", "2", "--slots", "3", "--stub-engine", str(ms)]
+           "--rounds", str(rounds), "--host-rounds", "1", "--warmup", "2", "--slots", "3", "--stub-engine", str(ms), "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -85,6 +86,31 @@ def test_backend_nccl_falls_back_to_gloo_when_rccl_does_not_come_up():
     assert d["n_gpus"] == 2 and d["extra"]["decoded_bases_total"] == 2 * 3 * 1100
     assert d["config"]["parallelism_bookkeeping"].startswith("gloo (cpu tensors) after RCCL bring-up failed on 2 of 2 ranks")
     assert "bookkeeping stays on gloo" in out.stderr
+
+
+def test_plain_line_times_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps (no extra regions: host_inclusive stays null without --full) and --dump-outputs
+    writes the last timed step's arrays as float .npy files -- the same arrays on a second run with the same arguments."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        out = _bench(["--gpus", "1", "--stub-engine", "2", "--steps", "7", "--warmup", "1", "--dump-outputs", str(d)])
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 7 and j["timed_steps"] == 7 and j["rounds"] == 1 and j["extra"]["host_inclusive"] is None
+        assert abs(j["ms_per_step"] - 1e3 * j["timed_region_s"] / 7) < 0.1
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in j
+        files = sorted(os.listdir(str(d)))
+        assert files and all(f.endswith(".npy") for f in files), files
+        arrays = {f: np.load(str(d / f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["decoded_values.npy"].shape == (1100,) and arrays["decoded_indices.npy"].shape == (1100, 2)
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
 
 
 def test_bench_refuses_a_launcher_whose_world_size_is_not_gpus():
