@@ -86,9 +86,14 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(float* __restrict__ x, co
   }
 }
 
-// 1x1 convolution of the one-channel signal (res_layer1 conv2a / branch1 conv1): out[(b, t)][c] = sig[b][t*stride] * w[c]
+// 1x1 convolution of the one-channel signal (res_layer1 conv2a / branch1 conv1): out[(b, t)][c] = sig[b][t*stride] * w[c], or with
+// `center` (the output goes through batch BN, which removes any per-channel constant) (sig[b][t*stride] - sig[0][0]) * w[c].  Raw
+// signal sits far from zero (~500 DAC counts): on a batch of a few positions the spread is a few counts, and BN of the uncentered
+// product cancels ~2 digits of float32 in the product, the mean and x * inv + (offset - mean * inv).  Centering at a sample of the
+// same batch keeps the values at the scale of their spread.
 __global__ __launch_bounds__(256) void rank1_conv_kernel(const float* __restrict__ sig, const float* __restrict__ w, float* __restrict__ out,
-                                                         long n_pos, int T_out, int L, int stride, int C) {
+                                                         long n_pos, int T_out, int L, int stride, int C, int center) {
+  const float c_sig = center ? sig[0] : 0.f;
   const int c4n = C / 4;
   const long total = n_pos * c4n;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(256) void rank1_conv_kernel(const float* __restrict
     const int c0 = (int)(i - pos * c4n) * 4;
     const long b = pos / T_out;
     const int t = (int)(pos - b * T_out);
-    const float xv = sig[b * L + (long)t * stride];
+    const float xv = sig[b * L + (long)t * stride] - c_sig;
     const f32x4 wv = *reinterpret_cast<const f32x4*>(w + c0);
     *reinterpret_cast<f32x4*>(out + pos * C + c0) = wv * xv;
   }
@@ -130,8 +135,8 @@ void launch_bn_apply(float* x, const double* sums, const float* scale, const flo
   hipLaunchKernelGGL(bn_apply_kernel, dim3(2048), dim3(256), 0, stream, x, sums, scale, offset, M, C, relu, add, add_sums, add_scale,
                      add_offset);
 }
-void launch_rank1_conv(const float* sig, const float* w, float* out, long n_pos, int T_out, int L, int stride, int C, hipStream_t stream) {
-  hipLaunchKernelGGL(rank1_conv_kernel, dim3(2048), dim3(256), 0, stream, sig, w, out, n_pos, T_out, L, stride, C);
+void launch_rank1_conv(const float* sig, const float* w, float* out, long n_pos, int T_out, int L, int stride, int C, bool center, hipStream_t stream) {
+  hipLaunchKernelGGL(rank1_conv_kernel, dim3(2048), dim3(256), 0, stream, sig, w, out, n_pos, T_out, L, stride, C, center ? 1 : 0);
 }
 
 }  // namespace chiron

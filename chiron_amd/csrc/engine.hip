@@ -1226,7 +1226,7 @@ static bool run_cnn_batch_bn(chiron_engine* e, Slot* s, int B, const float* sig)
     Prof pr(e, s, PN_CONV, 2.0 * ((double)Min * b.c_in * C + (double)Mout * (b.k * C + C + b.c_in) * C), 4.0 * (Min + 3.0 * Mout) * C * 3);
     // conv2a + BN + ReLU
     if (b.lift) {
-      launch_rank1_conv(sig, b.lift_a, A, Min, b.t_in, e->L, 1, C, s->stream);
+      launch_rank1_conv(sig, b.lift_a, A, Min, b.t_in, e->L, 1, C, true, s->stream);   // BN follows: centered (bn_batch.hip)
     } else {
       init_gemm(&g, e, b.ga, B);
       g.M = (int)Min;
@@ -1261,7 +1261,7 @@ static bool run_cnn_batch_bn(chiron_engine* e, Slot* s, int B, const float* sig)
     ok &= launch(e, g, s->stream);
     launch_bn_stats(Cf, Mout, C, s0, s->stream);
     if (b.lift) {
-      launch_rank1_conv(sig, b.res_a, D, Mout, b.t_out, e->L, b.stride, C, s->stream);
+      launch_rank1_conv(sig, b.res_a, D, Mout, b.t_out, e->L, b.stride, C, b.i_bn, s->stream);
     } else {
       init_gemm(&g, e, b.g1, B);
       g.M = (int)Mout;

@@ -1656,6 +1656,44 @@ def test_chiron_call_rna_mode_on_the_reference_rna_example(tmp_path):
             assert fq[1] == ce.index2base(np.argmax(cons, axis=0)).replace("T", "U")
 
 
+def test_chiron_call_rna_preset_on_the_reference_rna_example(tmp_path):
+    """`chiron call --mode rna -p rna-pre` (entry.py presets: batch 300, segment 2000, jump 1900, beam 30) on the same five reads: the
+    RNA topology at T = 400, i.e. on F(4,3) conv2b, with windows overlapping by 100 samples.  The meta line carries the preset; each
+    read's segments equal the oracle's beam search of the engine's own logits and the consensus equals the glue vote over them."""
+    import json
+    import shutil
+    from chiron_amd import assembly, entry, signal_io, eval as ce
+    from oracle import c_oracle
+    ex = os.path.join(GOLDEN, "example_rna")
+    digest = json.load(open(os.path.join(ex, "raw_digest.json")))
+    inp = tmp_path / "fast5"
+    inp.mkdir()
+    for name in digest:
+        shutil.copy(os.path.join(ex, name), str(inp / name))
+    out = str(tmp_path / "out")
+    model = os.path.join(os.path.dirname(os.path.abspath(ca.__file__)), "model", "RNA_default")
+    entry.main(["call", "-i", str(inp), "-o", out, "-m", model, "--mode", "rna", "-p", "rna-pre", "--synthetic-weights"])
+    spec, w, _ = ca.load_model(model, allow_synthetic=True)
+    with ca.Engine(spec, w, max_batch=300, segment_len=2000, max_beam=30) as eng:
+        assert eng.T == 400 and eng.ratio == 5.0
+        for name, d in digest.items():
+            stem = os.path.splitext(name)[0]
+            fq = open(os.path.join(out, "result", stem + ".fastq")).read().split("\n")
+            assert fq[0] == "@" + stem and len(fq[1]) == len(fq[3]) > 0 and set(fq[1]) <= set("ACGU")
+            meta = open(os.path.join(out, "meta", stem + ".meta")).read().split("\n")
+            assert meta[3].split() == [str(len(fq[1])), "300", "2000", "1900", "0"]
+            ds = signal_io.read_data_for_eval(os.path.join(out, "raw", stem + ".signal"), 0, 1900, 2000)
+            assert ds.reads_n == -(-d["samples"] // 1900)
+            sl = ca.seq_len_for_engine(ds.event_length, eng.ratio)
+            res = eng.infer(ds.event, sl, beam_width=30, want_logits=True)
+            rows, _ = c_oracle.beam(res.logits, sl, 30)
+            bp = [ce.index2base(r) for r in rows if len(r)]
+            seg = open(os.path.join(out, "segments", stem + ".fastq")).read().split("\n")
+            assert seg[1::2][:len(bp)] == bp and len(seg) == 2 * len(bp) + 1
+            cons = assembly.simple_assembly(bp, 1900 / 2000, kernal="glue")
+            assert fq[1] == ce.index2base(np.argmax(cons, axis=0)).replace("T", "U")
+
+
 @pytest.mark.parametrize("beam", [0, 30])
 def test_compact_decode_and_piecewise_submit_equal_the_sparse_tensor_path(dna, beam):
     """The host pipeline's fast path (round 5): chiron_engine_submit_pieces copies the cross-read pieces of a batch straight into the
@@ -1932,6 +1970,17 @@ def test_native_pipeline_equals_the_python_pipeline(dna, tmp_path, beam):
     path) against the Python thread pools it replaces, behind the REAL engine: raw/, reference/, result/, segments/ byte for byte and the
     non-timing lines of meta/, greedy and beam search, reads cut across batches and a partial last batch (population BN: a window's
     decode does not depend on its batch).  tests/test_pipeline_native.py is the same comparison behind a null engine, on CPU."""
+    _native_equals_python(dna, tmp_path, beam, 400, 390)
+
+
+@pytest.mark.parametrize("beam", [0, 5])
+def test_native_pipeline_equals_the_python_pipeline_at_odd_geometry(dna, tmp_path, beam):
+    """The same comparison at segment 257 / jump 250: an odd frame count (direct conv2b), windows overlapping by 7 samples, and
+    the window grid shifted against the batch boundaries."""
+    _native_equals_python(dna, tmp_path, beam, 257, 250)
+
+
+def _native_equals_python(dna, tmp_path, beam, L, jump):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import test_pipeline_native as tp
@@ -1946,9 +1995,10 @@ def test_native_pipeline_equals_the_python_pipeline(dna, tmp_path, beam):
     write_multi_read_fast5(os.path.join(inp, "r_multi.fast5"), [("read_%d" % k, "m%d" % k, sig[6][k * 9000:(k + 1) * 9000 + 17].astype(np.int16),
                                                                  "@q\nACGT\n+\n!!!!\n" if k == 0 else None) for k in range(3)])
     trees = {}
-    with ca.Engine(spec, w, max_batch=300, segment_len=400, n_slots=3, max_beam=beam) as eng:
+    with ca.Engine(spec, w, max_batch=300, segment_len=L, n_slots=3, max_beam=beam) as eng:
         for which in ("python", "native"):
-            F = tp._flags(inp, str(tmp_path / which), python_pipeline=(which == "python"), batch_size=300, beam=beam, model="synthetic")
+            F = tp._flags(inp, str(tmp_path / which), python_pipeline=(which == "python"), batch_size=300, beam=beam, model="synthetic",
+                          segment_len=L, jump=jump)
             ex.prepare_folders(F)
             files = ex.list_fast5(inp)
             assert ce.native_pipeline_ok(F, eng, files) == (which == "native")
