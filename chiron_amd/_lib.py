@@ -22,6 +22,8 @@ BN_POPULATION, BN_BATCH = 0, 1
 F32, F16, F32_SPLIT, F16_W2 = 0, 1, 2, 3
 X_ON_DEVICE, WANT_PROB, WANT_LOGITS, NO_DECODE_COPY, COMPACT_DECODE = 1, 2, 4, 8, 16
 KERNAL_GLUE, KERNAL_STICK, KERNAL_SIMPLE = 1, 2, 3
+CTC_WANT_GRAD, CTC_TRUSTED = 1, 2
+CTC_MAX_T, CTC_MAX_LABEL = 8192, 1 << 24
 
 
 class ResBlock(C.Structure):
@@ -112,6 +114,11 @@ SYMBOLS = [
     ("chiron_fast5_fastq", C.c_int, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int64]),
     ("chiron_write_signal_text", C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_char_p]),
     ("chiron_pipeline_run", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int64, C.POINTER(PipelineOpts), C.POINTER(PipelineStats)]),
+    ("chiron_ctc_workspace_size", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("chiron_ctc_loss", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_engine_score", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     ("chiron_last_error", C.c_char_p, []),
     ("chiron_device_pci_bus_id", C.c_int, [C.c_int32, C.c_char_p, C.c_size_t]),
     ("chiron_abi_version", C.c_int32, []),

@@ -280,6 +280,16 @@ struct Slot {
   const float* rnn_out = nullptr;   // the last layer's lasth (time-major [T][BP][lasth_ld]; rnn_out_f32 = false: halves)
   bool rnn_out_f32 = true;
   std::vector<ProfEvent> events;
+  // chiron_engine_score: labels, outputs and the edit-distance workspace of the scored batch; grown on demand, freed on destroy
+  struct ScoreBufs {
+    int32_t* labels = nullptr;     // [cap_labels]
+    int32_t* label_len = nullptr;  // [cap_rows]
+    float* loss = nullptr;         // [cap_rows]
+    float* edit = nullptr;         // [cap_rows]
+    int32_t* status = nullptr;     // [cap_rows]
+    uint64_t* ws = nullptr;        // [cap_ws] edit-distance bit vectors
+    size_t cap_labels = 0, cap_rows = 0, cap_ws = 0;
+  } score;
 };
 
 struct chiron_engine {
@@ -1059,6 +1069,9 @@ extern "C" void chiron_engine_destroy(chiron_engine* e) {
       hipEventDestroy(ev.b);
     }
     if (s.stream) hipStreamDestroy(s.stream);
+    void* sp[] = {s.score.labels, s.score.label_len, s.score.loss, s.score.edit, s.score.status, s.score.ws};
+    for (void* q : sp)
+      if (q) hipFree(q);
     void* hp[] = {s.h_sig, s.h_seq, s.h_indices, s.h_values, s.h_meta, s.h_log_prob, s.h_prob, s.h_logits, s.h_labels, s.h_count};
     free(s.h_flat);
     for (void* q : hp)
@@ -1835,6 +1848,83 @@ extern "C" chiron_status chiron_engine_device_results(chiron_engine* e, int32_t 
   if (values) *values = s->values;
   if (nnz_and_shape) *nnz_and_shape = s->meta;
   return CHIRON_OK;
+}
+
+// chiron_model.loss (chiron_model.py:50-75) + prediction's edit distance (:101-132) on the slot's last collected batch: device logits,
+// device seq_len and the device SparseTensor the decode left behind (enqueue_decode runs launch_sparse on every path)
+template <class Tp>
+static chiron_status grow(Tp** p, size_t* cap, size_t need) {
+  if (need <= *cap && *p) return CHIRON_OK;
+  if (*p) HIP_TRY(hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  HIP_TRY(hipMalloc((void**)p, (need ? need : 1) * sizeof(Tp)));
+  *cap = need;
+  return CHIRON_OK;
+}
+
+extern "C" chiron_status chiron_engine_score(chiron_engine* e, int32_t slot, const int32_t* labels, const int32_t* label_len, int32_t batch,
+                                             int32_t max_label_len, uint32_t flags, float* loss_out, float* edit_out, int32_t* status_out) {
+  if (!e) return fail(CHIRON_ERR_INVALID, "null engine");
+  if (slot < 0 || slot >= (int)e->slots.size()) return fail(CHIRON_ERR_STATE, "slot %d out of range", slot);
+  if (flags != 0) return fail(CHIRON_ERR_INVALID, "chiron_engine_score: flags must be 0");
+  if (!label_len || (!labels && max_label_len > 0) || !loss_out || !edit_out || !status_out || max_label_len < 0)
+    return fail(CHIRON_ERR_INVALID, "chiron_engine_score: null operand or negative max_label_len");
+  Slot* s = &e->slots[slot];
+  if (s->state.v.load(std::memory_order_acquire) != 0) return fail(CHIRON_ERR_STATE, "slot %d holds an uncollected batch", slot);
+  if (s->batch <= 0) return fail(CHIRON_ERR_STATE, "no batch has been collected on slot %d", slot);
+  if (batch != s->batch) return fail(CHIRON_ERR_STATE, "chiron_engine_score: batch %d, the slot's collected batch has %d rows", batch, s->batch);
+  if (e->K != CHIRON_CLASSES) return fail(CHIRON_ERR_INVALID, "chiron_engine_score: CTC over %d classes (A,C,G,T,blank expected)", e->K);
+  chiron_status st = ctc_check_rows(nullptr, labels, label_len, batch, e->T, max_label_len);
+  if (st) return st;
+  int S_ws = 0;
+  size_t ws_bytes = 0;
+  if ((st = ctc_sizes(batch, e->T, max_label_len, 0, &S_ws, &ws_bytes))) return st;
+  if (ctc_lds_bytes(S_ws) > 160 * 1024) return fail(CHIRON_ERR_OVERFLOW, "chiron_engine_score: %d CTC states per frame", S_ws);
+  HIP_TRY(hipSetDevice(e->opts.device_id));
+  Slot::ScoreBufs& sb = s->score;
+  const int words = (max_label_len + 63) / 64;
+  const size_t n_lab = (size_t)batch * max_label_len;
+  if ((st = grow(&sb.labels, &sb.cap_labels, n_lab))) return st;
+  if ((st = grow(&sb.ws, &sb.cap_ws, (size_t)batch * 6 * (words ? words : 1)))) return st;
+  if ((size_t)batch > sb.cap_rows || !sb.status) {   // the four per-row buffers grow together
+    size_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    sb.cap_rows = 0;
+    if ((st = grow(&sb.label_len, &c0, (size_t)batch)) || (st = grow(&sb.loss, &c1, (size_t)batch)) ||
+        (st = grow(&sb.edit, &c2, (size_t)batch)) || (st = grow(&sb.status, &c3, (size_t)batch)))
+      return st;
+    sb.cap_rows = batch;
+  }
+  auto run = [&]() -> chiron_status {
+    if (n_lab) HIP_TRY(hipMemcpyAsync(sb.labels, labels, n_lab * 4, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(sb.label_len, label_len, (size_t)batch * 4, hipMemcpyHostToDevice, s->stream));
+    CtcParams p;
+    p.logits = s->logits;
+    p.seq_len = s->seq;
+    p.labels = sb.labels;
+    p.label_len = sb.label_len;
+    p.B = batch;
+    p.T = e->T;
+    p.Lmax = max_label_len;
+    p.S_ws = S_ws;
+    p.S_lds = S_ws;
+    p.loss = sb.loss;
+    p.grad = nullptr;
+    p.alpha = nullptr;
+    p.status = sb.status;
+    if (launch_ctc(p, false, s->stream) != 0) return fail(CHIRON_ERR_DEVICE, "chiron_engine_score: CTC launch failed");
+    EditParams ep{s->indices, s->values, s->meta, sb.labels, sb.label_len, batch, max_label_len, words ? words : 1, sb.ws, sb.edit};
+    launch_edit(ep, s->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(loss_out, sb.loss, (size_t)batch * 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(edit_out, sb.edit, (size_t)batch * 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(status_out, sb.status, (size_t)batch * 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return CHIRON_OK;
+  };
+  st = run();
+  if (st) hipStreamSynchronize(s->stream);
+  return st;
 }
 
 // getcnnfeature (cnn.py:334-371): the [batch, T, C] feature tensor the CNN handed to the recurrent layers for the batch

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/chiron_amd.h"
+
 #define CHIRON_KMAX 5  // classes upper bound (reference: class_n = 5, rnn.py:25)
 
 namespace chiron {
@@ -282,5 +284,39 @@ void launch_bn_apply(float* x, const double* sums, const float* scale, const flo
                      const double* add_sums, const float* add_scale, const float* add_offset, hipStream_t stream);
 void launch_rank1_conv(const float* sig, const float* w, float* out, long n_pos, int T_out, int L, int stride, int C, bool center,
                        hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------------
+// CTC loss / gradient / edit distance (ctc_loss.hip): chiron_model.loss (chiron_model.py:50-75), prediction (:101-132)
+// ---------------------------------------------------------------------------------------------
+struct CtcParams {
+  const float* logits;       // [B][T][5]
+  const int32_t* seq_len;    // [B] (clamped to 0..T in the kernels)
+  const int32_t* labels;     // [B][Lmax] 0..3
+  const int32_t* label_len;  // [B] 0..Lmax
+  int B, T, Lmax;
+  int S_ws;                  // states per frame row of the alpha workspace: 2 min(Lmax, T) + 1
+  int S_lds;                 // states the LDS row of the recursions holds (the same bound)
+  float* loss;               // [B]
+  float* grad;               // [B][T][5] (backward only)
+  double* alpha;             // [B][T][S_ws] or null (loss only)
+  int32_t* status;           // [B] 0 scored / 1 skipped / 2 infeasible, or null
+};
+size_t ctc_lds_bytes(int S_lds);
+int launch_ctc(const CtcParams& p, bool want_grad, hipStream_t stream);  // 0 on success
+
+struct EditParams {
+  const int64_t* indices;    // [nnz][2] the decode's SparseTensor, rows ascending
+  const int64_t* values;     // [nnz]
+  const int64_t* meta;       // [0] = nnz
+  const int32_t* labels;     // [B][Lmax]
+  const int32_t* label_len;  // [B]
+  int B, Lmax, words;        // words = ceil(Lmax / 64)
+  uint64_t* ws;              // [B][6][words]
+  float* edit;               // [B]
+};
+void launch_edit(const EditParams& p, hipStream_t stream);
+// host side (ctc_loss.hip): row checks (seq_len may be null) and workspace sizes, shared with chiron_engine_score
+chiron_status ctc_check_rows(const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int batch, int T, int Lmax);
+chiron_status ctc_sizes(int64_t batch, int64_t T, int64_t Lmax, uint32_t flags, int* S_ws, size_t* bytes);
 
 }  // namespace chiron

@@ -193,6 +193,23 @@ class Engine(object):
         self._keep[slot] = (logits, seq_len)
         return self.collect(slot)
 
+    def score(self, slot, labels, label_len):
+        """chiron_model.loss (chiron_model.py:50-75, per row) and prediction's normalized edit distance (:101-132) of the batch last
+        collected on `slot` (chiron_engine_score): labels int [batch, max_label_len] 0..3 padded, label_len [batch] (host arrays).
+        -> (loss float32 [batch], edit float32 [batch], status int32 [batch]: 0 scored, 1 skipped, 2 infeasible)."""
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        label_len = np.ascontiguousarray(label_len, dtype=np.int32)
+        if labels.ndim != 2 or label_len.ndim != 1 or labels.shape[0] != label_len.shape[0]:
+            raise ValueError("labels must be [batch, max_label_len] with one label_len per row")
+        batch, lmax = labels.shape
+        loss = np.empty(batch, dtype=np.float32)
+        edit = np.empty(batch, dtype=np.float32)
+        status = np.empty(batch, dtype=np.int32)
+        _lib.check(self._lib.chiron_engine_score(self._h, slot, labels.ctypes.data_as(C.c_void_p), label_len.ctypes.data_as(C.c_void_p),
+                                                 batch, lmax, 0, loss.ctypes.data_as(C.c_void_p), edit.ctypes.data_as(C.c_void_p),
+                                                 status.ctypes.data_as(C.c_void_p)))
+        return loss, edit, status
+
     def features(self, slot=0):
         """getcnnfeature (cnn.py:334-371): the CNN feature tensor [batch, T, C] of the batch last run on the (idle) slot."""
         b, c = C.c_int32(), C.c_int32()

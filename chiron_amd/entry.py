@@ -119,6 +119,61 @@ def evaluation(args):
     return out
 
 
+def validate(args):
+    """Score a model on labelled windows, as the reference's training loop validates (chiron_model.loss, chiron_model.py:50-75, and
+    prediction, :101-132): windows from a folder of .signal + .label pairs (labelled.py, chiron_input.py:429-525), the engine's
+    logits and decode, then per row the CTC loss and the normalized edit distance on the GPU (Engine.score).  seq_len is what
+    `chiron call` feeds (seq_len_for_engine: round half even of len / ratio, chiron_eval.py:337); the reference's training loop
+    truncates len / ratio instead, which differs only where the ratio does not divide the length (RNA, ratio 5).  Writes a JSON
+    report to args.output and returns it."""
+    import json
+    import numpy as np
+    from . import ctc, labelled, model as model_mod
+    from .engine import Engine, seq_len_for_engine
+    ds = labelled.read_raw_data_sets(args.input, seq_length=args.segment_len, max_segments=args.max_segments, sig_norm=args.sig_norm)
+    n = ds.event.shape[0]
+    if n == 0:
+        raise ValueError("no labelled window under %s" % args.input)
+    spec, weights, _ = model_mod.load_model(args.model, allow_synthetic=args.synthetic_weights)
+    batches, losses, edits, stats = [], [], [], []
+    with Engine(spec, weights, max_batch=min(args.batch_size, n), segment_len=args.segment_len, device_id=args.device,
+                max_beam=args.beam, dtype=args.dtype, calibrate=not args.no_calibration) as eng:
+        for i in range(0, n, args.batch_size):
+            x = np.ascontiguousarray(ds.event[i:i + args.batch_size], dtype=np.float32)
+            sl = seq_len_for_engine(ds.event_length[i:i + args.batch_size], eng.ratio)
+            ll = ds.label_length[i:i + args.batch_size]
+            dense = labelled.dense_labels(ds.label[i:i + args.batch_size], ll)
+            eng.submit(0, x, sl, beam_width=args.beam, want_prob=False)
+            eng.collect(0)
+            loss, edit, status = eng.score(0, dense, ll)
+            losses.append(loss)
+            edits.append(edit)
+            stats.append(status)
+            kept = status != ctc.STATUS_INFEASIBLE
+            batches.append({"loss_mean": float(np.mean(np.where(kept, loss, 0.0)[kept], dtype=np.float64)) if kept.any() else None,
+                            "error_mean": float(np.mean(edit, dtype=np.float64)), "n": int(x.shape[0]),
+                            "skipped": int(np.count_nonzero(status == ctc.STATUS_SKIPPED)),
+                            "infeasible": int(np.count_nonzero(status == ctc.STATUS_INFEASIBLE))})
+    loss = np.concatenate(losses)
+    edit = np.concatenate(edits)
+    status = np.concatenate(stats)
+    kept = status != ctc.STATUS_INFEASIBLE
+    summary = {"windows": int(n), "files": len(set(ds.files)),
+               # tf.reduce_mean of the per-row losses: skipped rows count as 0 (their loss is 0), infeasible rows -- where TF raises --
+               # are left out and counted
+               "loss_mean_reference": float(np.mean(loss[kept], dtype=np.float64)) if kept.any() else None,
+               "skipped": int(np.count_nonzero(status == ctc.STATUS_SKIPPED)), "infeasible": int(np.count_nonzero(~kept)),
+               "error_mean": float(np.mean(edit, dtype=np.float64))}
+    if args.fl_gamma > 0:
+        summary["fl_gamma"] = args.fl_gamma
+        summary["focal_loss_mean_reference"] = float(np.mean(ctc.focal(loss[kept], args.fl_gamma))) if kept.any() else None
+    report = {"model": args.model, "input": args.input, "segment_len": args.segment_len, "batch_size": args.batch_size,
+              "beam": args.beam, "dtype": args.dtype, "sig_norm": args.sig_norm, "batches": batches, "summary": summary}
+    with open(args.output, "w") as f:
+        json.dump(report, f, indent=1)
+    return report
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -163,6 +218,23 @@ def build_parser():
     p.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
                    help="Use seeded synthetic weights when the model folder has no checkpoint data.")
     p.set_defaults(func=evaluation)
+    v = subparsers.add_parser("validate", description="Score a model on labelled .signal/.label pairs: CTC loss and edit distance",
+                              help="CTC loss and normalized edit distance against known bases.")
+    v.add_argument("-i", "--input", required=True, help="Folder of .signal files with their .label files.")
+    v.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder path")
+    v.add_argument("-o", "--output", required=True, help="JSON report path")
+    v.add_argument("-l", "--segment_len", type=int, default=400, help="Window length (the reference's sequence_len).")
+    v.add_argument("-b", "--batch_size", type=int, default=1100, help="Batch size.")
+    v.add_argument("--beam", type=int, default=30, help="Beam width of the decoder for the edit distance, 0 = greedy.")
+    v.add_argument("--sig_norm", default="none", choices=["none", "median", "mean"], help="Signal normalisation.")
+    v.add_argument("--fl_gamma", type=float, default=0.0, help="Focal-loss gamma of the reported focal variant (0: none).")
+    v.add_argument("--max_segments", type=int, default=None, help="Largest number of windows to read.")
+    v.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    v.add_argument("--dtype", default="fp32", choices=["fp32", "fp16", "fp16-w2", "fp32-split"], help="Engine arithmetic.")
+    v.add_argument("--no-calibration", dest="no_calibration", action="store_true", help="--dtype fp16: skip the bias correction.")
+    v.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
+                   help="Use seeded synthetic weights when the model folder has no checkpoint data.")
+    v.set_defaults(func=validate)
     return parser
 
 

@@ -395,6 +395,54 @@ chiron_status chiron_crc32c(const void* data, size_t len, uint32_t* out);
  * The reference has no counterpart: it is one process on one device (chiron_eval.py:255-262).  cap >= 16.            */
 chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap);
 
+/* CTC loss and its gradient, chiron/chiron_model.py:50-75 loss(): tf.nn.ctc_loss(label, logits, seq_len, ctc_merge_repeated=True,
+ * time_major=False, ignore_longer_outputs_than_inputs=True) per window (the mean, and the focal term fl_gamma, are left to the caller).
+ * Classes A,C,G,T = 0..3 (chiron_input.py:710-730 base2ind), blank = 4 (the last class); labels are NOT collapsed beforehand
+ * (preprocess_collapse_repeated=False), so a repeat needs a blank between its two frames.  loss = -log p(label | logits) with a
+ * log-softmax over the 5 classes of every frame; frames t >= seq_len[b] are ignored and get a zero gradient.  The gradient is with
+ * respect to the LOGITS (pre-softmax), as TF returns it: softmax(t,k) - posterior(t,k).
+ * Rows with label_len > seq_len: loss 0, gradient 0 (skipped, ignore_longer_outputs_than_inputs).  Rows that fit by length but not
+ * once every repeat has its blank (label_len + repeats > seq_len): loss +inf, gradient 0 (infeasible).  TF raises "Not enough time
+ * for target transition sequence" there; a batch call cannot raise per row.  This rule is recalled TF behaviour, not a measurement
+ * of TF.  label_len 0 is legal: the loss is -sum_t log softmax(t, blank).
+ *
+ * The recursions run in double (log space); the loss is rounded to float at the end.
+ * Workspace: with CHIRON_CTC_WANT_GRAD the forward pass keeps alpha of every frame, in double, for the backward pass,
+ *   bytes = batch * T * S_max * 8,   S_max = 2 * min(max_label_len, T) + 1,
+ * and 0 bytes without it.  Host-only (no GPU needed).  CHIRON_ERR_OVERFLOW when T > CHIRON_CTC_MAX_T or max_label_len >
+ * CHIRON_CTC_MAX_LABEL; within those bounds every workspace stays below 2^62 bytes and every offset the kernels form is 64-bit.  */
+#define CHIRON_CTC_WANT_GRAD 1u
+#define CHIRON_CTC_TRUSTED 2u   /* chiron_ctc_loss: the caller has checked seq_len / labels / label_len: no read-back, no sync */
+#define CHIRON_CTC_MAX_T 8192
+#define CHIRON_CTC_MAX_LABEL (1 << 24)
+chiron_status chiron_ctc_workspace_size(int32_t batch, int32_t T, int32_t max_label_len, uint32_t flags, size_t* bytes);
+
+/* Stand-alone CTC loss (and, with CHIRON_CTC_WANT_GRAD, its gradient) for torch users: every operand is a device pointer on
+ * device_id.  logits float32 [batch, T, 5]; seq_len int32 [batch]; labels int32 [batch, max_label_len] dense, padded; label_len
+ * int32 [batch]; loss_out float32 [batch]; grad_out float32 [batch, T, 5] (written only with CHIRON_CTC_WANT_GRAD); workspace of
+ * chiron_ctc_workspace_size bytes (NULL without the flag).  Asynchronous on `stream` (a hipStream_t; NULL = the null stream), with
+ * one exception: seq_len, labels and label_len are first read back on `stream` (a small synchronous copy) and checked, so that an
+ * argument error returns CHIRON_ERR_INVALID before anything is launched: a label outside 0..3, label_len < 0 or > max_label_len,
+ * seq_len < 0 or > T, batch < 0.  With CHIRON_CTC_TRUSTED that read-back is skipped and the call is fully asynchronous; the
+ * kernels then clamp seq_len to 0..T and label_len to 0..max_label_len and read labels modulo 4 (memory-safe, but the result of
+ * an unchecked bad argument is unspecified).  Deterministic: the same bits run to run.                                                       */
+chiron_status chiron_ctc_loss(int32_t device_id, const float* logits, const int32_t* seq_len, const int32_t* labels,
+                              const int32_t* label_len, int32_t batch, int32_t T, int32_t max_label_len, uint32_t flags,
+                              float* loss_out, float* grad_out, void* workspace, void* stream);
+
+/* Score the slot's most recent COLLECTED batch against known bases, as the reference's validation does: the CTC loss above on the
+ * batch's device logits and seq_len (chiron_model.py:50-75, fl_gamma and the mean left to the caller) and
+ * tf.edit_distance(decoded, label, normalize=True) (chiron_model.py:101-132) of the batch's device decode -- the SparseTensor
+ * (indices, values) every decode path leaves on the device (greedy, beam, chiron_engine_decode, CHIRON_COMPACT_DECODE) -- against
+ * the labels: Levenshtein distance / truth length; an empty truth gives 0 against an empty decode and +inf otherwise (recalled TF
+ * behaviour).  labels int32 [batch, max_label_len] and label_len [batch] are HOST arrays; loss_out, edit_out [batch] float32 and
+ * status_out [batch] int32 (0 = scored, 1 = skipped, 2 = infeasible; see chiron_ctc_workspace_size) are host arrays too.  Runs on
+ * the slot's stream with no host round trip of logits or decode and synchronises that stream before returning.  The engine's label
+ * and workspace buffers grow on demand and are freed by chiron_engine_destroy.  flags: 0 (reserved).  CHIRON_ERR_STATE when no
+ * batch has been collected on the slot, the slot holds an uncollected batch, or batch differs from the collected batch's size.   */
+chiron_status chiron_engine_score(chiron_engine* e, int32_t slot, const int32_t* labels, const int32_t* label_len, int32_t batch,
+                                  int32_t max_label_len, uint32_t flags, float* loss_out, float* edit_out, int32_t* status_out);
+
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
 /* What kind of build this library is.  CHIRON_BUILD_TIMING: at least one object was compiled as a timing-only kernel variant
