@@ -119,6 +119,13 @@ SYMBOLS = [
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("chiron_engine_score", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    ("chiron_rnn_params_range", C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("chiron_rnn_train_sizes", C.c_int, [C.POINTER(ModelDesc), C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("chiron_rnn_train_forward", C.c_int, [C.c_int32, C.POINTER(ModelDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_rnn_train_backward", C.c_int, [C.c_int32, C.POINTER(ModelDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_engine_device_features", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("chiron_last_error", C.c_char_p, []),
     ("chiron_device_pci_bus_id", C.c_int, [C.c_int32, C.c_char_p, C.c_size_t]),
     ("chiron_abi_version", C.c_int32, []),

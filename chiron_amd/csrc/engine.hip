@@ -1954,6 +1954,24 @@ extern "C" chiron_status chiron_engine_features(chiron_engine* e, int32_t slot, 
   return CHIRON_OK;
 }
 
+// The device pointer behind chiron_engine_features: the frozen CNN's output reaches a trainer (chiron_rnn_train_forward) without a
+// host round trip.  Same slot-state rules; fp32 engines only (the other dtypes keep features as halves or hi/lo pairs).
+extern "C" chiron_status chiron_engine_device_features(chiron_engine* e, int32_t slot, const float** out_ptr, int32_t* out_batch,
+                                                       int32_t* out_channels) {
+  if (!e) return fail(CHIRON_ERR_INVALID, "null engine");
+  if (slot < 0 || slot >= (int)e->slots.size()) return fail(CHIRON_ERR_STATE, "slot %d out of range", slot);
+  Slot* s = &e->slots[slot];
+  if (s->state.v.load(std::memory_order_acquire) != 0) return fail(CHIRON_ERR_STATE, "slot %d holds an uncollected batch", slot);
+  if (s->net_batch < 1 || s->sig_used == nullptr)
+    return fail(CHIRON_ERR_STATE, "slot %d holds no network batch (nothing submitted yet, or its last batch was decode-only)", slot);
+  if (e->split || e->f16) return fail(CHIRON_ERR_INVALID, "chiron_engine_device_features: fp32 engines only");
+  if (!out_ptr) return fail(CHIRON_ERR_INVALID, "chiron_engine_device_features: null out_ptr");
+  *out_ptr = (const float*)s->sig_used;
+  if (out_batch) *out_batch = s->net_batch;
+  if (out_channels) *out_channels = e->C;
+  return CHIRON_OK;
+}
+
 // Bias correction of the f16 engine (post-training-quantisation style, data dependent only through per-channel MEANS of a
 // calibration batch): run the network, measure the mean of every input channel of every f16 weight matrix, move
 // sum_k E[x_k] (f16(W) - W)[n][k] out of the shift / LSTM bias of output n.  Upstream corrections move downstream means a little,

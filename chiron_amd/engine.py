@@ -220,6 +220,13 @@ class Engine(object):
         _lib.check(self._lib.chiron_engine_features(self._h, slot, out.ctypes.data_as(C.c_void_p), out.size, C.byref(b), C.byref(c)))
         return out
 
+    def device_features(self, slot=0):
+        """The same tensor where it lies: (device pointer, batch, channels) of float32 [batch, T, C] (chiron_engine_device_features),
+        valid until the next submit on the slot.  fp32 engines only."""
+        p, b, c = C.c_void_p(), C.c_int32(), C.c_int32()
+        _lib.check(self._lib.chiron_engine_device_features(self._h, slot, C.byref(p), C.byref(b), C.byref(c)))
+        return p.value, b.value, c.value
+
     def calibrate(self, x=None, seq_len=None, iterations=2):
         """f16 engines: bias correction for the weights' rounding to halves (chiron_engine_calibrate); a no-op for fp32 / fp32-split.
         x [n, segment_len] float32 calibration windows (default: `calibration_windows`, a fixed synthetic squiggle, so that every

@@ -174,6 +174,15 @@ def validate(args):
     return report
 
 
+def finetune(args):
+    """Adapt the recurrent stack and the FC head of a model to labelled reads, the CNN frozen: train.finetune (the loop of
+    chiron_rcnn_train.py:99-135 on the GPU)."""
+    import logging
+    from . import train
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    return train.finetune(args)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -235,6 +244,28 @@ def build_parser():
     v.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
                    help="Use seeded synthetic weights when the model folder has no checkpoint data.")
     v.set_defaults(func=validate)
+    t = subparsers.add_parser("finetune", description="Fine-tune the recurrent layers and the FC head on labelled .signal/.label pairs "
+                              "(CNN frozen)", help="Fine-tune the recurrent layers and the head on labelled reads.")
+    # names and defaults: chiron_rcnn_train.py:182-222
+    t.add_argument("-i", "--input", required=True, help="Folder of .signal files with their .label files.")
+    t.add_argument("-o", "--output", required=True, help="Folder the fine-tuned model is written to.")
+    t.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder to start from")
+    t.add_argument("-v", "--validation", default=None, help="validation folder (default: the training windows)")
+    t.add_argument("-s", "--sequence_len", type=int, default=400, help="the length of sequence")
+    t.add_argument("-b", "--batch_size", type=int, default=300, help="Batch size")
+    t.add_argument("-t", "--step_rate", type=float, default=4e-3, help="Step rate")
+    t.add_argument("-x", "--max_steps", type=int, default=10000, help="Maximum step")
+    t.add_argument("-n", "--segments_num", type=int, default=None, help="Maximum number of segments read into the training queue, default(None) read all.")
+    t.add_argument("--gradient_clip", type=float, default=None, help="Clip every variable's gradient to this norm.")
+    t.add_argument("--fl_gamma", type=float, default=0.0, help="Focal-loss gamma (0: plain CTC loss).")
+    t.add_argument("--opt_method", default="Adam", choices=["Adam", "SGD", "RMSProp", "Momentum"], help="Optimizer.")
+    t.add_argument("--sig_norm", default="none", choices=["none", "median", "mean"], help="Signal normalisation.")
+    t.add_argument("--report-every", dest="report_every", type=int, default=10, help="Steps between loss / validation reports.")
+    t.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    t.add_argument("--seed", type=int, default=1234, help="Seed of the batch order.")
+    t.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
+                   help="Use seeded synthetic weights when the model folder has no checkpoint data.")
+    t.set_defaults(func=finetune)
     return parser
 
 

@@ -1,5 +1,6 @@
 """TensorFlow checkpoint "tensor bundle" (V2) reader -- replaces tf.train.Saver.restore /
-tf.train.latest_checkpoint as used by the reference (chiron_eval.py:272-276).
+tf.train.latest_checkpoint as used by the reference (chiron_eval.py:272-276) -- and writer: what tf.train.Saver.save
+leaves behind (chiron_rcnn_train.py:110-113, :134), as far as the reader above and TF's own restore need it.
 
 `<prefix>.index` is a LevelDB-style immutable table: 48-byte footer
 (metaindex handle, index handle, magic), blocks of prefix-compressed entries with a restart array;
@@ -181,3 +182,90 @@ def read_tensors(prefix, entries=None, names=None, verify=True):
                               % (data_path, name, e["crc32c"]))
             out[name] = np.frombuffer(raw, dtype=_NP[e["dtype"]]).reshape(e["shape"]).copy()
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# writer: tf.train.Saver.save (chiron_rcnn_train.py:110-113, :134)
+# ---------------------------------------------------------------------------------------------
+def _put_varint(v):
+    out = bytearray()
+    while True:
+        b = v & 0x7F
+        v >>= 7
+        out.append(b | 0x80 if v else b)
+        if not v:
+            return bytes(out)
+
+
+def _mask(c):
+    return ((((c >> 15) | (c << 17)) & 0xFFFFFFFF) + 0xA282EAD8) & 0xFFFFFFFF
+
+
+def _table_block(entries, restart_interval=16):
+    """One LevelDB table block: prefix-compressed (key, value) pairs in key order, then the restart array."""
+    buf, restarts, prev = bytearray(), [], b""
+    for i, (key, value) in enumerate(entries):
+        shared = 0
+        if i % restart_interval == 0:
+            restarts.append(len(buf))
+        else:
+            while shared < min(len(prev), len(key)) and prev[shared] == key[shared]:
+                shared += 1
+        buf += _put_varint(shared) + _put_varint(len(key) - shared) + _put_varint(len(value)) + key[shared:] + value
+        prev = key
+    for r in restarts or [0]:
+        buf += struct.pack("<I", r)
+    buf += struct.pack("<I", len(restarts) or 1)
+    return bytes(buf)
+
+
+def _entry_proto(dtype, shape, offset, size, crc):
+    dims = b"".join(b"\x12" + _put_varint(len(d)) + d for d in (b"\x08" + _put_varint(int(n)) for n in shape))
+    out = b"\x08" + _put_varint(dtype) + b"\x12" + _put_varint(len(dims)) + dims
+    if offset:
+        out += b"\x20" + _put_varint(offset)
+    return out + b"\x28" + _put_varint(size) + b"\x35" + struct.pack("<I", crc)
+
+
+def write_bundle(prefix, tensors, block_entries=40):
+    """Write {name: array} as <prefix>.index + <prefix>.data-00000-of-00001 (one shard, no compression): float32 / int32 / int64
+    arrays keep their type, everything else becomes float32.  Every BundleEntryProto carries the masked CRC-32C of its tensor's
+    bytes (chiron_crc32c), every table block its trailer checksum, as tensor_bundle.cc / table_builder.cc write them."""
+    items = {}
+    for name, a in tensors.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            a = a.astype(np.float32)
+        items[name] = np.array(a, dtype=a.dtype.newbyteorder("<"), order="C")   # (ascontiguousarray would turn a scalar into [1])
+    codes = {np.dtype("<f4"): DT_FLOAT, np.dtype("<i4"): DT_INT32, np.dtype("<i8"): DT_INT64}
+    entries = [(b"", b"\x08\x01\x12\x02\x08\x01")]     # BundleHeaderProto {num_shards = 1, version {producer = 1}}
+    offset = 0
+    with open(prefix + ".data-00000-of-00001", "wb") as f:
+        for name in sorted(items, key=lambda k: k.encode("utf-8")):
+            raw = items[name].tobytes()
+            f.write(raw)
+            entries.append((name.encode("utf-8"), _entry_proto(codes[items[name].dtype], items[name].shape, offset, len(raw),
+                                                               masked_crc32c(raw))))
+            offset += len(raw)
+    table, handles = bytearray(), []
+
+    def put(block):
+        handle = (len(table), len(block))
+        table.extend(block + b"\x00" + struct.pack("<I", _mask(crc32c(block + b"\x00"))))   # type 0 = uncompressed
+        return handle
+
+    for i in range(0, len(entries), block_entries):
+        chunk = entries[i:i + block_entries]
+        handles.append((chunk[-1][0],) + put(_table_block(chunk)))
+    meta = put(_table_block([]))
+    index = put(_table_block([(k, _put_varint(o) + _put_varint(n)) for k, o, n in handles], restart_interval=1))
+    foot = _put_varint(meta[0]) + _put_varint(meta[1]) + _put_varint(index[0]) + _put_varint(index[1])
+    table += foot + b"\x00" * (40 - len(foot)) + struct.pack("<Q", MAGIC)
+    with open(prefix + ".index", "wb") as f:
+        f.write(bytes(table))
+
+
+def write_checkpoint_file(model_dir, name):
+    """The text proto `checkpoint` that tf.train.latest_checkpoint reads (CheckpointState, relative paths as Saver.save writes)."""
+    with open(os.path.join(model_dir, "checkpoint"), "w") as f:
+        f.write('model_checkpoint_path: "%s"\nall_model_checkpoint_paths: "%s"\n' % (name, name))

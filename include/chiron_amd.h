@@ -443,6 +443,50 @@ chiron_status chiron_ctc_loss(int32_t device_id, const float* logits, const int3
 chiron_status chiron_engine_score(chiron_engine* e, int32_t slot, const int32_t* labels, const int32_t* label_len, int32_t batch,
                                   int32_t max_label_len, uint32_t flags, float* loss_out, float* edit_out, int32_t* status_out);
 
+/* Training seam of the recurrent stack and the FC head: what chiron_rcnn_train.py:99-109 (sess.run([net.ctc_loss, net.step])) needs
+ * between the CNN's feature tensor and the logits, for the variables of rnn.py:20-97 (DNA), :99-174 (RNA) and the head :72-96.  The
+ * CNN stays frozen; fp32 only; hidden 100 and 5 classes (CHIRON_ERR_INVALID otherwise).  Optimizer and loss stay with the caller
+ * (chiron_model.py:77-99 train_opt; chiron_ctc_loss above gives d loss / d logits).
+ *
+ * The trainable parameter vector IS a slice of the weight blob of chiron_weights_size, in that layout: from the first
+ * lstm_cell/kernel to rnn_fnn_layer/bias_class.  chiron_rnn_params_range returns where it starts and how long it is (floats);
+ * gradients come back in the same layout.  Host-only.                                                                            */
+chiron_status chiron_rnn_params_range(const chiron_model_desc* desc, size_t* first_float, size_t* n_floats);
+
+/* Bytes of the tape (what the forward pass keeps for the backward pass: the transposed features, every layer's output, and per
+ * step, row and direction the four activated gates and the cell state) and of the workspace (x-projections, gate derivatives,
+ * dh buffers, split-K partial sums) for one batch of `batch` windows of T frames.  Both grow linearly in the batch rounded up to
+ * 16 rows.  Host-only (no GPU needed).  CHIRON_ERR_INVALID: batch < 1, T < 1, unsupported topology.  CHIRON_ERR_OVERFLOW: T >
+ * CHIRON_CTC_MAX_T, batch > 2^20, or T * roundup(batch, 16) > 2^24 rows; within those bounds every offset the kernels form is
+ * 64-bit.  The launchers below make the same checks.                                                                              */
+chiron_status chiron_rnn_train_sizes(const chiron_model_desc* desc, int32_t batch, int32_t T, size_t* tape_bytes, size_t* workspace_bytes);
+
+/* Forward with a tape (rnn.py:20-174 + :72-96 in training): logits_out [batch, T, 5] from features [batch, T, C] (the tensor of
+ * chiron_engine_features) and seq_len int32 [batch], with the semantics of the inference layers: gate order i, j, f, o; forget bias
+ * +1.0; frames t >= seq_len[b] emit 0 and carry the state; the backward direction runs over the first seq_len[b] frames reversed
+ * (seq_len is clamped to 0..T).  params: the slice of chiron_rnn_params_range.  Every pointer is device memory on device_id; tape
+ * and workspace of chiron_rnn_train_sizes bytes, uninitialised.  Asynchronous on `stream` (a hipStream_t; NULL = the null stream);
+ * argument errors are reported before anything is launched.                                                                       */
+chiron_status chiron_rnn_train_forward(int32_t device_id, const chiron_model_desc* desc, const float* params, const float* features,
+                                       const int32_t* seq_len, int32_t batch, int32_t T, float* logits_out, void* tape, void* workspace,
+                                       void* stream);
+
+/* Backward of the call above (tf.gradients behind opt.minimize, chiron_rcnn_train.py:52-62): from dlogits [batch, T, 5] and the
+ * tape that chiron_rnn_train_forward filled for the SAME params, features, seq_len, batch and T, dparams_out receives d loss / d
+ * params in the layout of the slice, and dfeatures_out [batch, T, C] (may be NULL) d loss / d features: exactly 0 at frames t >=
+ * seq_len[b].  Every reduction over the T * batch rows goes through per-slice partial sums in the workspace and a second pass in
+ * slice order, never through float atomics: the same bits run to run.  The workspace may be the forward's (its content is not
+ * needed).  Asynchronous on `stream`; argument errors are reported before anything is launched.                                   */
+chiron_status chiron_rnn_train_backward(int32_t device_id, const chiron_model_desc* desc, const float* params, const float* features,
+                                        const int32_t* seq_len, const float* dlogits, int32_t batch, int32_t T, const void* tape,
+                                        void* workspace, float* dparams_out, float* dfeatures_out, void* stream);
+
+/* The device pointer behind chiron_engine_features (getcnnfeature, cnn.py:334-371): float32 [batch, T, C] of the batch most recently
+ * run on an idle slot, valid until the next submit on that slot; written on the slot's stream, which chiron_engine_collect has
+ * synchronised.  fp32 engines only (CHIRON_ERR_INVALID otherwise); CHIRON_ERR_STATE as chiron_engine_features.  The frozen CNN's
+ * output reaches the trainer above without a host round trip.                                                                     */
+chiron_status chiron_engine_device_features(chiron_engine* e, int32_t slot, const float** ptr, int32_t* batch, int32_t* channels);
+
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
 /* What kind of build this library is.  CHIRON_BUILD_TIMING: at least one object was compiled as a timing-only kernel variant

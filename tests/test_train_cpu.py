@@ -1,0 +1,129 @@
+"""CPU tests of the training seam: the float64 reference against the oracle, the host-only ABI queries, the checkpoint writer and the
+`finetune` command line."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import chiron_amd as ca
+from chiron_amd import _lib, entry, tf_bundle, train
+
+import rnn_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("kind", ["dna", "rna"])
+def test_rnn_ref_float64_forward_equals_the_oracle(kind):
+    from oracle import nn_oracle
+    spec = ca.dna_default_spec() if kind == "dna" else ca.rna_default_spec()
+    w = ca.synthetic_weights(spec, seed=7)
+    rng = np.random.default_rng(3)
+    B, T = 6, 17
+    fea = rng.normal(size=(B, T, 256))
+    sl = np.array([0, 1, T, 9, 4, 16])
+    ref = nn_oracle.fc_head(nn_oracle.rnn_forward(fea, sl, spec.to_dict(), w), w)
+    got, _, _ = rnn_ref.forward(fea, sl, spec, w)
+    assert np.abs(got.numpy() - ref).max() <= 1e-12
+
+
+@pytest.mark.parametrize("spec", [ca.dna_default_spec(), ca.rna_default_spec()], ids=["DNA_default", "RNA_default"])
+def test_params_range_equals_the_offsets_of_the_variables(built, spec):
+    names = list(spec.variables())
+    sizes = [int(np.prod(s)) for s in spec.variables().values()]
+    first_name = spec.lstm_scope(0, "fw") + "kernel"
+    first = sum(sizes[:names.index(first_name)])
+    assert names[-1] == "rnn_fnn_layer/bias_class"
+    assert train.params_range(spec) == (first, sum(sizes) - first)
+    off = 0
+    for name, (o, shape) in train.param_layout(spec).items():
+        assert o == off and tuple(spec.variables()[name]) == shape
+        off += int(np.prod(shape))
+    assert off == sum(sizes) - first
+
+
+def test_train_sizes_grow_linearly_in_the_batch(built):
+    spec = ca.dna_default_spec()
+    t16, w16 = train.train_sizes(spec, 16, 400)
+    t32, w32 = train.train_sizes(spec, 32, 400)
+    t48, w48 = train.train_sizes(spec, 48, 400)
+    assert t32 == 2 * t16 and t48 == 3 * t16        # the tape is per row
+    assert t32 - t16 == t48 - t32 > 0
+    assert train.train_sizes(spec, 17, 400) == (t32, w32)     # rows padded to 16
+    # the workspace: per-row buffers + split-K partials that depend on the row count only through a capped slice count
+    t3200, w3200 = train.train_sizes(spec, 3200, 400)
+    t6400, w6400 = train.train_sizes(spec, 6400, 400)
+    t9600, w9600 = train.train_sizes(spec, 9600, 400)
+    assert w6400 - w3200 == w9600 - w6400 > 0 and w32 > w16
+
+
+def _sizes_status(spec, batch, T):
+    desc = spec.to_c()
+    a, b = C.c_size_t(), C.c_size_t()
+    return _lib.load().chiron_rnn_train_sizes(C.byref(desc), batch, T, C.byref(a), C.byref(b))
+
+
+def test_train_sizes_refuse_bad_shapes(built):
+    spec = ca.dna_default_spec()
+    assert _sizes_status(spec, 16, 0) == _lib.ERR_INVALID
+    assert _sizes_status(spec, 16, -3) == _lib.ERR_INVALID
+    assert _sizes_status(spec, 0, 400) == _lib.ERR_INVALID
+    assert _sizes_status(spec, 16, 8193) == _lib.ERR_OVERFLOW          # T > CHIRON_CTC_MAX_T
+    assert _sizes_status(spec, 1 << 19, 400) == _lib.ERR_OVERFLOW      # T * batch > 2^24 rows
+    assert _sizes_status(spec, (1 << 20) + 1, 1) == _lib.ERR_OVERFLOW
+    small = ca.dna_default_spec()
+    small.hidden = 64
+    assert _sizes_status(small, 16, 400) == _lib.ERR_INVALID           # the kernels are built for hidden 100
+    desc = small.to_c()
+    a, b = C.c_size_t(), C.c_size_t()
+    assert _lib.load().chiron_rnn_params_range(C.byref(desc), C.byref(a), C.byref(b)) == _lib.ERR_INVALID
+
+
+def test_write_bundle_round_trip_and_crc(built, tmp_path):
+    rng = np.random.default_rng(2)
+    tensors = {"a/%03d/w" % i: rng.normal(size=(3, i + 1)).astype(np.float32) for i in range(90)}
+    tensors["global_step"] = np.asarray(77, dtype=np.int64)
+    tensors["flags"] = np.arange(5, dtype=np.int32)
+    prefix = str(tmp_path / "x.ckpt-77")
+    tf_bundle.write_bundle(prefix, tensors)
+    entries = tf_bundle.read_index(prefix + ".index")
+    assert sorted(entries) == sorted(tensors)
+    got = tf_bundle.read_tensors(prefix, entries, list(tensors))
+    for k, v in tensors.items():
+        assert got[k].dtype == v.dtype and got[k].shape == v.shape and got[k].tobytes() == v.tobytes(), k
+    data = prefix + ".data-00000-of-00001"
+    raw = bytearray(open(data, "rb").read())
+    raw[len(raw) // 2] ^= 0x10
+    open(data, "wb").write(bytes(raw))
+    with pytest.raises(IOError, match="checksum mismatch"):
+        tf_bundle.read_tensors(prefix, entries, list(tensors))
+
+
+@pytest.mark.parametrize("spec", [ca.dna_default_spec(), ca.rna_default_spec()], ids=["DNA_default", "RNA_default"])
+def test_saved_model_loads_through_load_model(built, tmp_path, spec):
+    w = ca.synthetic_weights(spec, seed=11)
+    out = str(tmp_path / "model")
+    train.save_model(out, spec, w, 123, train.config_for(spec, None, "Adam", 2.0))
+    assert tf_bundle.latest_checkpoint(out).endswith("final.ckpt-123")
+    spec2, w2, config = ca.load_model(out)
+    assert spec2.to_dict() == spec.to_dict() and config["opt_method"] == "Adam"
+    canon = spec.canonical_weights(w)
+    assert list(w2) == list(canon)
+    for k in canon:
+        assert np.asarray(w2[k]).tobytes() == np.asarray(canon[k], dtype=np.float32).tobytes(), k
+
+
+def test_finetune_command_line_defaults():
+    a = entry.build_parser().parse_args(["finetune", "-i", "in", "-o", "out"])
+    assert a.func is entry.finetune
+    assert (a.sequence_len, a.batch_size, a.step_rate, a.max_steps, a.segments_num) == (400, 300, 4e-3, 10000, None)
+    assert (a.gradient_clip, a.fl_gamma, a.opt_method, a.sig_norm, a.device, a.validation) == (None, 0.0, "Adam", "none", 0, None)
+    assert a.synthetic_weights is False and isinstance(a.seed, int)
+    assert a.model.endswith(os.path.join("model", "DNA_default"))
+    b = entry.build_parser().parse_args(["finetune", "-i", "in", "-o", "out", "-v", "val", "-s", "300", "-b", "16", "-t", "1e-3", "-x", "40",
+                                         "-n", "500", "--gradient_clip", "5", "--fl_gamma", "2", "--opt_method", "Momentum",
+                                         "--sig_norm", "median", "--device", "1", "--seed", "3", "--synthetic-weights"])
+    assert (b.validation, b.sequence_len, b.batch_size, b.step_rate, b.max_steps, b.segments_num) == ("val", 300, 16, 1e-3, 40, 500)
+    assert (b.gradient_clip, b.fl_gamma, b.opt_method, b.sig_norm, b.device, b.seed, b.synthetic_weights) == \
+        (5.0, 2.0, "Momentum", "median", 1, 3, True)
