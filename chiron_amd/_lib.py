@@ -126,6 +126,14 @@ SYMBOLS = [
     ("chiron_rnn_train_backward", C.c_int, [C.c_int32, C.POINTER(ModelDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("chiron_engine_device_features", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("chiron_cnn_params_range", C.c_int, [C.POINTER(ModelDesc), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("chiron_cnn_train_sizes", C.c_int, [C.POINTER(ModelDesc), C.c_int32, C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("chiron_cnn_train_tape_relu", C.c_int, [C.POINTER(ModelDesc), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("chiron_cnn_train_forward", C.c_int, [C.c_int32, C.POINTER(ModelDesc), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_cnn_train_backward", C.c_int, [C.c_int32, C.POINTER(ModelDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("chiron_last_error", C.c_char_p, []),
     ("chiron_device_pci_bus_id", C.c_int, [C.c_int32, C.c_char_p, C.c_size_t]),
     ("chiron_abi_version", C.c_int32, []),

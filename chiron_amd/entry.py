@@ -183,6 +183,14 @@ def finetune(args):
     return train.finetune(args)
 
 
+def train(args):
+    """Train every variable of the network on labelled reads: train.train_network (the loop of chiron_rcnn_train.py:99-135 on the GPU)."""
+    import logging
+    from . import train as train_mod
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    return train_mod.train_network(args)
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -266,6 +274,32 @@ def build_parser():
     t.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
                    help="Use seeded synthetic weights when the model folder has no checkpoint data.")
     t.set_defaults(func=finetune)
+    r = subparsers.add_parser("train", description="Train the whole network (CNN, recurrent layers, FC head) on labelled .signal/.label pairs",
+                              help="Train the whole network on labelled reads.")
+    # names and defaults: chiron_rcnn_train.py:180-225
+    r.add_argument("-i", "--input", required=True, help="Folder of .signal files with their .label files.")
+    r.add_argument("-o", "--output", required=True, help="Folder the trained model is written to.")
+    r.add_argument("-m", "--model", type=str, default=None, help="model folder to start from (default: a from-scratch initialisation)")
+    r.add_argument("-v", "--validation", default=None, help="validation folder (default: the training windows)")
+    r.add_argument("-s", "--sequence_len", type=int, default=400, help="the length of sequence")
+    r.add_argument("-b", "--batch_size", type=int, default=300, help="Batch size")
+    r.add_argument("-t", "--step_rate", type=float, default=4e-3, help="Step rate")
+    r.add_argument("-x", "--max_steps", type=int, default=10000, help="Maximum step")
+    r.add_argument("-n", "--segments_num", type=int, default=None, help="Maximum number of segments read into the training queue, default(None) read all.")
+    r.add_argument("--configure", default=None, help="Model structure configure json file (a model.json) of a from-scratch model.")
+    r.add_argument("--gradient_clip", type=float, default=None, help="Clip every variable's gradient to this norm.")
+    r.add_argument("--retrain", dest="retrain", action="store_true", help="Continue from the newest checkpoint under -o.")
+    r.add_argument("--bn", default="batch", choices=["population", "batch"],
+                   help="BN naming of a from-scratch model: batch (HEAD's simple_global_bn, no statistics stored) or population.")
+    r.add_argument("--fl_gamma", type=float, default=0.0, help="Focal-loss gamma (0: plain CTC loss).")
+    r.add_argument("--opt_method", default="Adam", choices=["Adam", "SGD", "RMSProp", "Momentum"], help="Optimizer.")
+    r.add_argument("--sig_norm", default="none", choices=["none", "median", "mean"], help="Signal normalisation.")
+    r.add_argument("--report-every", dest="report_every", type=int, default=10, help="Steps between loss / validation reports.")
+    r.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    r.add_argument("--seed", type=int, default=1234, help="Seed of the batch order and of the initialisation.")
+    r.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
+                   help="Use seeded synthetic weights when the model folder has no checkpoint data.")
+    r.set_defaults(func=train, retrain=False)
     return parser
 
 

@@ -238,15 +238,19 @@ def batch_loss(logits, seq_len, labels, label_len, fl_gamma=0.0):
 
 def save_model(out_dir, spec, weights, step, config):
     """<out>/model.json, checkpoint and final.ckpt-<step>.{index,data-00000-of-00001} (chiron_rcnn_train.py:110-113, :134), loadable
-    through model.load_model."""
+    through model.load_model, under the variable names of the model's own BN naming (ModelSpec.variables())."""
     from . import tf_bundle
-    if spec.bn_mode != "population":
-        raise ValueError("only population-BN models are saved (the CNN is frozen on its population statistics)")
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "model.json"), "w") as f:
         json.dump(config, f)
     canon = spec.canonical_weights(weights)
-    tensors = OrderedDict((name, np.asarray(canon[name], dtype=np.float32).reshape(shape)) for name, shape in spec.variables().items())
+    # a batch-BN model (cnn.py:181-186 naming) stores scale and offset under its own names and no statistics
+    alias = {}
+    for site, _, has_bn in spec._sites():
+        if has_bn:
+            alias.update((name, site + "_bn/" + leaf) for leaf, name in zip(spec.BN_LEAVES, spec.bn_names(site)) if name is not None)
+    tensors = OrderedDict((name, np.asarray(canon[alias.get(name, name)], dtype=np.float32).reshape(shape))
+                          for name, shape in spec.variables().items())
     tensors["global_step"] = np.asarray(step, dtype=np.int64)
     name = "final.ckpt-%d" % step
     tf_bundle.write_bundle(os.path.join(out_dir, name), tensors)
@@ -340,5 +344,350 @@ def finetune(args):
     report = {"input": args.input, "model": args.model, "checkpoint": prefix, "steps": args.max_steps, "batch_size": bsz,
               "windows": int(n), "opt_method": args.opt_method, "step_rate": args.step_rate, "reports": reports}
     with open(os.path.join(args.output, "finetune.json"), "w") as f:
+        json.dump(report, f, indent=1)
+    return report
+
+
+# ---------------------------------------------------------------------------------------------
+# the whole network: CNN seam + recurrent seam, `chiron train`
+# ---------------------------------------------------------------------------------------------
+BN_DECAY = 0.99   # cnn.py:125 batchnorm(decay=0.99)
+
+
+def cnn_params_range(spec):
+    """(first float, float count) of the CNN section of the weight blob (chiron_cnn_params_range)."""
+    first, n = C.c_size_t(), C.c_size_t()
+    desc = spec.to_c()
+    _lib.check(_lib.load().chiron_cnn_params_range(C.byref(desc), C.byref(first), C.byref(n)))
+    return int(first.value), int(n.value)
+
+
+def cnn_train_sizes(spec, batch, segment_len):
+    """(tape bytes, workspace bytes) of one batch (chiron_cnn_train_sizes).  Host-only."""
+    tape, ws = C.c_size_t(), C.c_size_t()
+    desc = spec.to_c()
+    _lib.check(_lib.load().chiron_cnn_train_sizes(C.byref(desc), int(batch), int(segment_len), C.byref(tape), C.byref(ws)))
+    return int(tape.value), int(ws.value)
+
+
+def cnn_param_layout(spec):
+    """Ordered {canonical name: (offset in the CNN section, shape)}: the entries of blob_layout() before the first lstm_cell/kernel."""
+    rnn = set(name for name, _ in spec._rnn_and_head())
+    out, off = OrderedDict(), 0
+    for name, shape in spec.blob_layout().items():
+        if name in rnn:
+            break
+        out[name] = (off, tuple(shape))
+        off += int(np.prod(shape))
+    return out
+
+
+def cnn_forward(spec, params, signal):
+    """chiron_cnn_train_forward on torch CUDA tensors (float32 params [n], signal [B, L], contiguous) -> (features [B, T, C], moments
+    [n] with the pop_mean / pop_var slots holding the batch's mean / biased variance and zeros elsewhere, tape, workspace)."""
+    torch = _torch()
+    B, L = signal.shape
+    tape_b, ws_b = cnn_train_sizes(spec, B, L)
+    dev = signal.device
+    feats = torch.empty((B, spec.output_len(L), spec.blocks[-1]["out"]), dtype=torch.float32, device=dev)
+    moments = torch.zeros_like(params)
+    tape = torch.empty(tape_b, dtype=torch.uint8, device=dev)
+    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    desc = spec.to_c()
+    _lib.check(_lib.load().chiron_cnn_train_forward(_device_index(signal), C.byref(desc), params.data_ptr(), signal.data_ptr(), B, L,
+                                                    feats.data_ptr(), moments.data_ptr(), tape.data_ptr(), ws.data_ptr(),
+                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return feats, moments, tape, ws
+
+
+def cnn_tape_relu(spec, tape, batch, segment_len):
+    """Ordered {name: float32 view [batch, frames, channels] into `tape`} of the ReLU outputs the forward kept
+    (chiron_cnn_train_tape_relu): the stem's site name, per block <block>/branch2/conv2a, <block>/branch2/conv2b and <block>/out.
+    `view > 0` is the mask the backward uses."""
+    torch = _torch()
+    names = ([spec.STEM_SITE] if spec.stem else []) + [b["name"] + leaf for b in spec.blocks
+                                                        for leaf in ("/branch2/conv2a", "/branch2/conv2b", "/out")]
+    floats = tape.view(torch.float32)
+    desc = spec.to_c()
+    out = OrderedDict()
+    for i, name in enumerate(names):
+        off, frames, ch = C.c_size_t(), C.c_int32(), C.c_int32()
+        _lib.check(_lib.load().chiron_cnn_train_tape_relu(C.byref(desc), int(batch), int(segment_len), i, C.byref(off), C.byref(frames),
+                                                          C.byref(ch)))
+        n = int(batch) * frames.value * ch.value
+        out[name] = floats[off.value:off.value + n].view(int(batch), frames.value, ch.value)
+    return out
+
+
+def cnn_backward(spec, params, signal, dfeatures, tape, ws):
+    """chiron_cnn_train_backward -> dparams [n] (exactly 0 in the pop_mean / pop_var slots)."""
+    torch = _torch()
+    B, L = signal.shape
+    dparams = torch.empty_like(params)
+    desc = spec.to_c()
+    _lib.check(_lib.load().chiron_cnn_train_backward(_device_index(signal), C.byref(desc), params.data_ptr(), signal.data_ptr(),
+                                                     dfeatures.data_ptr(), B, L, tape.data_ptr(), ws.data_ptr(), dparams.data_ptr(),
+                                                     C.c_void_p(torch.cuda.current_stream(signal.device).cuda_stream)))
+    return dparams
+
+
+_NET_FN = None
+
+
+def _network_function():
+    global _NET_FN
+    if _NET_FN is not None:
+        return _NET_FN
+    torch = _torch()
+
+    class NetworkFunction(torch.autograd.Function):
+        """(logits, moments) = f(flat, signal, seq_len, spec): the CNN seam chained into the recurrent seam with no copy; backward
+        runs chiron_rnn_train_backward, hands its dfeatures to chiron_cnn_train_backward and returns the two sections side by side."""
+
+        @staticmethod
+        def forward(ctx, flat, signal, seq_len, spec):
+            p = flat.detach().contiguous()
+            n_cnn = cnn_params_range(spec)[1]
+            pc, pr = p[:n_cnn], p[n_cnn:]
+            feats, moments, ctape, cws = cnn_forward(spec, pc, signal)
+            logits, rtape, rws = rnn_forward(spec, pr, feats, seq_len)
+            ctx.spec, ctx.n_cnn = spec, n_cnn
+            ctx.tapes = (ctape, cws, rtape, rws)
+            ctx.save_for_backward(p, signal, seq_len, feats)
+            ctx.mark_non_differentiable(moments)
+            return logits, moments
+
+        @staticmethod
+        def backward(ctx, dlogits, _dmoments):
+            p, signal, seq_len, feats = ctx.saved_tensors
+            ctape, cws, rtape, rws = ctx.tapes
+            pc, pr = p[:ctx.n_cnn], p[ctx.n_cnn:]
+            d_rnn, dfeat = rnn_backward(ctx.spec, pr, feats, seq_len, dlogits.to(torch.float32).contiguous(), rtape, rws, True)
+            d_cnn = cnn_backward(ctx.spec, pc, signal, dfeat, ctape, cws)
+            ctx.tapes = None
+            return torch.cat([d_cnn, d_rnn]), None, None, None
+
+    _NET_FN = NetworkFunction
+    return _NET_FN
+
+
+class Network(object):
+    """torch.nn.Module over the whole network of `spec`: one flat float32 CUDA parameter `flat` in the weight blob's layout
+    (ModelSpec.blob_layout(): the CNN section, then the recurrent section that RecurrentHead owns), forward(signal [B, L],
+    seq_len [B]) -> logits [B, T, 5].  Batch normalisation uses the batch's moments in every forward (training semantics); in
+    train() mode each forward also moves the statistics: pop = 0.99 * pop + 0.01 * batch (cnn.py:153-156, biased variance).  The
+    pop_mean / pop_var slots get a zero gradient.  The module class is built on first use so that importing this file needs no torch."""
+
+    def __new__(cls, spec, weights, device=None):
+        return _network_class()(spec, weights, device)
+
+
+_NET = None
+
+
+def _network_class():
+    global _NET
+    if _NET is not None:
+        return _NET
+    torch = _torch()
+
+    class _Network(torch.nn.Module):
+        def __init__(self, spec, weights, device=None):
+            torch.nn.Module.__init__(self)
+            self.spec = spec
+            blob = spec.pack(weights)
+            (c0, cn), (r0, rn) = cnn_params_range(spec), params_range(spec)
+            if c0 != 0 or r0 != cn or r0 + rn != blob.size:
+                raise ValueError("the CNN and the recurrent sections do not tile the weight blob")
+            self.layout, off = OrderedDict(), 0
+            for name, shape in spec.blob_layout().items():
+                self.layout[name] = (off, tuple(shape))
+                off += int(np.prod(shape))
+            dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+            self.flat = torch.nn.Parameter(torch.from_numpy(blob.copy()).to(dev))
+            stat = np.concatenate([np.arange(o, o + int(np.prod(sh))) for name, (o, sh) in self.layout.items()
+                                   if name.endswith(("_bn/pop_mean", "_bn/pop_var"))])
+            self.register_buffer("stat_index", torch.from_numpy(stat).to(dev), persistent=False)
+            self.last_moments = None
+
+        def named_views(self, tensor=None):
+            """Ordered {canonical variable name: view} into the parameter (or into `tensor`, e.g. its .grad)."""
+            t = self.flat if tensor is None else tensor
+            return OrderedDict((name, t[off:off + int(np.prod(shape))].view(*shape)) for name, (off, shape) in self.layout.items())
+
+        def forward(self, signal, seq_len):
+            if not (signal.is_cuda and signal.dim() == 2):
+                raise ValueError("signal must be a CUDA tensor [batch, segment_len]: the training kernels have no CPU fallback")
+            signal = signal.to(torch.float32).contiguous()
+            seq_len = seq_len.to(device=signal.device, dtype=torch.int32).contiguous()
+            if seq_len.shape != (signal.shape[0],):
+                raise ValueError("seq_len must be [batch]")
+            logits, moments = _network_function().apply(self.flat, signal, seq_len, self.spec)
+            self.last_moments = moments
+            if self.training:
+                # the tensor saved for backward aliases `flat`; changing the statistics' slots under it is harmless because neither
+                # chiron_cnn_train_forward nor _backward reads them
+                with torch.no_grad():
+                    idx = self.stat_index
+                    self.flat.data[idx] = BN_DECAY * self.flat.data[idx] + (1.0 - BN_DECAY) * moments[idx]
+            return logits
+
+        def state_weights(self):
+            """The full canonical weights dict of the current parameters, ready for Engine(spec, weights, ...) and save_model."""
+            host = self.flat.detach().cpu().numpy()
+            return OrderedDict((name, host[off:off + int(np.prod(shape))].reshape(shape).copy()) for name, (off, shape) in self.layout.items())
+
+    _NET = _Network
+    return _NET
+
+
+def _truncated_normal(rng, stddev, shape):
+    """tf.truncated_normal: N(0, stddev^2) redrawn outside two standard deviations."""
+    out = rng.normal(0.0, stddev, shape)
+    bad = np.abs(out) > 2.0 * stddev
+    while bad.any():
+        out[bad] = rng.normal(0.0, stddev, int(bad.sum()))
+        bad = np.abs(out) > 2.0 * stddev
+    return out.astype(np.float32)
+
+
+def init_weights(spec, seed=1234):
+    """From-scratch weights under the canonical names of spec.blob_layout(), following the reference's initialisers IN DISTRIBUTION;
+    numpy's random stream, not TF's: no draw is bit-compatible with a TF run.
+
+    - convolution filters (cnn.py:42-45): tf.contrib.layers.xavier_initializer(uniform=False) = truncated normal (two sigma) of
+      pre-truncation deviation sqrt(1.3 * 2 / (fan_in + fan_out)), fan = k * channels: a sample deviation of sqrt(2 / (fan_in + fan_out));
+    - population-BN sites (cnn.py:141-148): scale = 0.1; offset = tf.get_variable's default, Glorot uniform on [size]: U(+-sqrt(3 / size));
+      pop_mean = 0, pop_var = 1;
+    - batch-BN sites (cnn.py:181-186): scale and offset both tf.contrib.layers.variance_scaling_initializer() (factor 2, fan-in,
+      truncated normal): pre-truncation deviation sqrt(1.3 * 2 / size) around ZERO; the statistics' slots hold 0 / 1 and are not saved;
+    - lstm_cell/kernel: LSTMCell's default, Glorot uniform U(+-sqrt(6 / (rows + 4 H))); lstm_cell/bias = 0;
+    - head (rnn.py:72-96): weights tf.truncated_normal_initializer(stddev=sqrt(2 / (2 H))), weights_class stddev sqrt(2 / H)
+      (pre-truncation deviations), both biases 0."""
+    rng = np.random.RandomState(seed)
+    H = spec.hidden
+    w = OrderedDict()
+    for site, shape, has_bn in spec._sites():
+        _, k, ci, co = shape
+        w[site + "/weights"] = _truncated_normal(rng, np.sqrt(1.3 * 2.0 / (k * ci + k * co)), shape)
+        if not has_bn:
+            continue
+        if spec.bn_mode == "population":
+            w[site + "_bn/scale"] = np.full(co, 0.1, dtype=np.float32)
+            lim = np.sqrt(3.0 / co)
+            w[site + "_bn/offset"] = rng.uniform(-lim, lim, co).astype(np.float32)
+        else:
+            w[site + "_bn/scale"] = _truncated_normal(rng, np.sqrt(1.3 * 2.0 / co), (co,))
+            w[site + "_bn/offset"] = _truncated_normal(rng, np.sqrt(1.3 * 2.0 / co), (co,))
+        w[site + "_bn/pop_mean"] = np.zeros(co, dtype=np.float32)
+        w[site + "_bn/pop_var"] = np.ones(co, dtype=np.float32)
+    for l in range(spec.rnn_layers):
+        for d in ("fw", "bw"):
+            rows = spec.lstm_in_width(l) + H
+            lim = np.sqrt(6.0 / (rows + 4 * H))
+            w[spec.lstm_scope(l, d) + "kernel"] = rng.uniform(-lim, lim, (rows, 4 * H)).astype(np.float32)
+            w[spec.lstm_scope(l, d) + "bias"] = np.zeros(4 * H, dtype=np.float32)
+    w["rnn_fnn_layer/weights"] = _truncated_normal(rng, np.sqrt(2.0 / (2 * H)), (2, H))
+    w["rnn_fnn_layer/bias"] = np.zeros(H, dtype=np.float32)
+    w["rnn_fnn_layer/weights_class"] = _truncated_normal(rng, np.sqrt(2.0 / H), (H, spec.classes))
+    w["rnn_fnn_layer/bias_class"] = np.zeros(spec.classes, dtype=np.float32)
+    return OrderedDict((k, w[k]) for k in spec.blob_layout())
+
+
+def _checkpoint_step(model_dir):
+    from . import tf_bundle
+    prefix = tf_bundle.latest_checkpoint(model_dir)
+    if prefix is None or not os.path.exists(prefix + ".index"):
+        return 0
+    entries = tf_bundle.read_index(prefix + ".index")
+    if "global_step" not in entries:
+        return 0
+    return int(tf_bundle.read_tensors(prefix, entries, ["global_step"])["global_step"])
+
+
+def train_network(args):
+    """The loop of chiron_rcnn_train.py:99-135 on every variable of cnn.py and rnn.py: `finetune`'s loop with Network in place of
+    engine + RecurrentHead.
+
+    The start: -m given, that model (either BN naming); --retrain, the newest checkpoint under -o with its global_step carried on
+    (the optimizer's state is NOT in a checkpoint written here: it restarts); neither, init_weights of the topology that --configure
+    (a model.json; default chiron_model.py:37-48's) names, with --bn batch (what HEAD builds) or population.  Batch normalisation
+    uses the batch's moments in every training step whatever the model's BN naming; a population-BN model's statistics move by
+    0.99 / 0.01 each step and are saved, a batch-BN model's are not saved.  Validation builds a second Engine from the current
+    weights in the model's own bn_mode (the reference validates with training=True, chiron_rcnn_train.py:116; that is not
+    reproduced).  Writes <out>/model.json, checkpoint, final.ckpt-<step>.* and train.json; returns the report dict."""
+    torch = _torch()
+    from . import labelled, model as model_mod
+    from .engine import Engine, seq_len_for_engine
+    if args.opt_method not in OPT_METHODS:
+        raise ValueError("opt_method %r: one of %s" % (args.opt_method, ", ".join(OPT_METHODS)))
+    torch.manual_seed(args.seed)
+    rng = np.random.RandomState(args.seed)
+    ds = labelled.read_raw_data_sets(args.input, seq_length=args.sequence_len, max_segments=args.segments_num, sig_norm=args.sig_norm)
+    n = ds.event.shape[0]
+    if n == 0:
+        raise ValueError("no labelled window under %s" % args.input)
+    vs = ds if not args.validation else labelled.read_raw_data_sets(args.validation, seq_length=args.sequence_len,
+                                                                  max_segments=args.segments_num, sig_norm=args.sig_norm)
+    step0 = 0
+    if args.retrain:
+        spec, weights, config = model_mod.load_model(args.output)
+        step0 = _checkpoint_step(args.output)
+    elif args.model:
+        spec, weights, config = model_mod.load_model(args.model, allow_synthetic=args.synthetic_weights)
+    else:
+        config = model_mod.read_config(args.configure)
+        spec = model_mod.spec_from_config(config, args.bn)
+        weights = init_weights(spec, args.seed)
+    bsz = min(args.batch_size, n)
+    dev = torch.device("cuda", args.device)
+    net = Network(spec, weights, device=args.device)
+    net.train()
+    opt = make_optimizer(args.opt_method, [net.flat], args.step_rate)
+    ratio = float(args.sequence_len) / spec.output_len(args.sequence_len)
+    reports, window = [], []
+
+    def validation_error(step_weights):
+        nv = min(bsz, vs.event.shape[0])
+        with Engine(spec, step_weights, max_batch=nv, segment_len=args.sequence_len, device_id=args.device) as ve:
+            x = np.ascontiguousarray(vs.event[:nv], dtype=np.float32)
+            sl = seq_len_for_engine(vs.event_length[:nv], ve.ratio)
+            ve.submit(0, x, sl, beam_width=0, want_prob=False)
+            ve.collect(0)
+            _, edit, _ = ve.score(0, labelled.dense_labels(vs.label[:nv], vs.label_length[:nv]), vs.label_length[:nv])
+        return float(np.mean(edit, dtype=np.float64))
+
+    def to_dev(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+
+    order, pos = rng.permutation(n), 0
+    for step in range(1, args.max_steps + 1):
+        if pos + bsz > n:
+            order, pos = rng.permutation(n), 0
+        rows = order[pos:pos + bsz]
+        pos += bsz
+        sl = seq_len_for_engine(ds.event_length[rows], ratio)
+        ll = ds.label_length[rows]
+        dense = labelled.dense_labels([ds.label[i] for i in rows], ll)
+        sl_d = to_dev(sl, np.int32)
+        logits = net(to_dev(ds.event[rows], np.float32), sl_d)
+        loss = batch_loss(logits, sl_d, to_dev(dense, np.int32), to_dev(ll, np.int32), args.fl_gamma)
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        if args.gradient_clip is not None:
+            clip_by_norm_(net.named_views(net.flat.grad), float(args.gradient_clip))
+        opt.step()
+        window.append(float(loss.item()))
+        if step % args.report_every == 0 or step == args.max_steps:
+            rep = {"step": step0 + step, "train_loss": float(np.mean(window)), "validation_error": validation_error(net.state_weights())}
+            window = []
+            reports.append(rep)
+            logger.info("Step %d, loss %.5f, edit_distance %.5f", rep["step"], rep["train_loss"], rep["validation_error"])
+    final = step0 + args.max_steps
+    prefix = save_model(args.output, spec, net.state_weights(), final, config_for(spec, config, args.opt_method, args.fl_gamma))
+    report = {"input": args.input, "model": args.model, "checkpoint": prefix, "steps": args.max_steps, "global_step": final,
+              "batch_size": bsz, "windows": int(n), "bn_mode": spec.bn_mode, "opt_method": args.opt_method, "step_rate": args.step_rate,
+              "reports": reports}
+    with open(os.path.join(args.output, "train.json"), "w") as f:
         json.dump(report, f, indent=1)
     return report

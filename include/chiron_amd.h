@@ -487,6 +487,55 @@ chiron_status chiron_rnn_train_backward(int32_t device_id, const chiron_model_de
  * output reaches the trainer above without a host round trip.                                                                     */
 chiron_status chiron_engine_device_features(chiron_engine* e, int32_t slot, const float** ptr, int32_t* batch, int32_t* channels);
 
+/* Training seam of the CNN: what chiron_rcnn_train.py:30-136 needs between the signal and the feature tensor, for every variable of
+ * cnn.py that ModelSpec describes (the optional stem conv_layer/conv1 and the residual blocks: branch1/conv1, branch2/conv2a,
+ * conv2b, conv2c with their BN sites).  fp32 only.  Batch normalisation ALWAYS uses the batch's own moments here, whatever
+ * desc->bn_mode says: biased variance over all batch * T_site positions of a site, epsilon float32(1e-5) (simple_global_bn,
+ * cnn.py:166-188; the training=True branch of batchnorm, cnn.py:151-158); the gradient flows through mean and variance.  The CNN
+ * does not see seq_len: the zero-padded tail of a short window takes part in the moments, as in the reference.
+ *
+ * The trainable parameter vector is the CNN section of the weight blob of chiron_weights_size, in that layout: everything before
+ * the first lstm_cell/kernel.  Every BN site has its four slots scale, offset, pop_mean, pop_var.  chiron_cnn_params_range returns
+ * where the section starts (0) and how long it is (floats); together with chiron_rnn_params_range it tiles the blob.  Host-only. */
+chiron_status chiron_cnn_params_range(const chiron_model_desc* desc, size_t* first_float, size_t* n_floats);
+
+/* Bytes of the tape (every BN site's convolution output and statistics, every ReLU output) and of the workspace (four
+ * activation-sized buffers, per-slice partial sums) for one batch of `batch` windows of segment_len samples.  Both grow linearly
+ * in the batch apart from a term of at most a few MB for the partial sums.  Host-only.  CHIRON_ERR_INVALID: batch < 1,
+ * segment_len < 1, unsupported topology (more than 2048 channels).  CHIRON_ERR_OVERFLOW: batch > 2^20, batch * segment_len > 2^24
+ * rows, or more than CHIRON_CTC_MAX_T output frames; within those bounds every offset the kernels form is 64-bit.  The launchers
+ * below make the same checks.                                                                                                    */
+chiron_status chiron_cnn_train_sizes(const chiron_model_desc* desc, int32_t batch, int32_t segment_len, size_t* tape_bytes,
+                                     size_t* workspace_bytes);
+
+/* Where the tape keeps ReLU output number `index` (network order: the stem's when there is one, then per block conv2a's, conv2b's
+ * and the block's output): float offset into the tape, frames per window and channels of the [batch, frames, channels] tensor.  The
+ * rest of the tape is opaque.  The sign pattern of these tensors is the set of ReLU masks the backward uses, which is what a check
+ * of the gradients against a smooth reference needs.  Host-only.  CHIRON_ERR_INVALID: index out of range; otherwise the statuses
+ * of chiron_cnn_train_sizes.                                                                                                    */
+chiron_status chiron_cnn_train_tape_relu(const chiron_model_desc* desc, int32_t batch, int32_t segment_len, int32_t index,
+                                         size_t* offset_floats, int32_t* frames, int32_t* channels);
+
+/* Forward with a tape: features_out [batch, T, C] (the layout chiron_rnn_train_forward takes) from signal [batch, segment_len].
+ * params: the section of chiron_cnn_params_range; its pop_mean / pop_var slots are not read.  moments_out has the layout of
+ * params; only the pop_mean / pop_var slots are written: each site's batch mean and biased variance (the moving averages are the
+ * caller's arithmetic, cnn.py:153-156).  Every pointer is device memory on device_id, 16-byte aligned; tape and workspace of
+ * chiron_cnn_train_sizes bytes, uninitialised.  Asynchronous on `stream` (a hipStream_t; NULL = the null stream); argument errors
+ * are reported before anything is launched.                                                                                      */
+chiron_status chiron_cnn_train_forward(int32_t device_id, const chiron_model_desc* desc, const float* params, const float* signal,
+                                       int32_t batch, int32_t segment_len, float* features_out, float* moments_out, void* tape,
+                                       void* workspace, void* stream);
+
+/* Backward of the call above: from dfeatures [batch, T, C] (dfeatures_out of chiron_rnn_train_backward) and the tape that
+ * chiron_cnn_train_forward filled for the SAME params, signal, batch and segment_len, dparams_out receives d loss / d params in
+ * the layout of the section; the pop_mean / pop_var slots receive exactly 0.  No gradient with respect to the signal is produced.
+ * Every reduction over rows (BN sums, weight gradients) goes through per-slice partial sums whose slice count depends on the
+ * shape alone and a second pass in slice order, never through float atomics: the same bits run to run.  The workspace may be
+ * the forward's (its content is not needed).  Asynchronous on `stream`; argument errors are reported before anything is launched. */
+chiron_status chiron_cnn_train_backward(int32_t device_id, const chiron_model_desc* desc, const float* params, const float* signal,
+                                        const float* dfeatures, int32_t batch, int32_t segment_len, const void* tape, void* workspace,
+                                        float* dparams_out, void* stream);
+
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
 /* What kind of build this library is.  CHIRON_BUILD_TIMING: at least one object was compiled as a timing-only kernel variant

@@ -1,0 +1,108 @@
+"""How far apart are float32 realisations of the CNN's forward and of its gradients?  Sets the factors of tests/test_gpu_cnn_train.py.
+
+Default mode, CPU only, the HIP result never enters: for every gradient case of tests/cnn_train_cases.py, float64 autograd of
+tests/cnn_ref.py gives the exact values; then the plain float32 run of the same restatement and DRAWS more float32 realisations of
+it (every convolution's channels in a permuted order, the batch in another order).  Per tensor: every member's error against
+float64, the median member's, and the largest member's ratio to that median.
+  forward    features and every site's moments, the network as it is;
+  gradients  under FIXED ReLU masks (the signs of the float64 pre-activations), as the GPU test compares them: with free masks a ReLU
+             whose pre-activation is within rounding of 0 flips between realisations and moves the gradient by a discrete amount
+             (max / median up to 3e4 was measured that way), which no bar of a few rounding errors can absorb.
+factor = max(4, 1.5 x the largest ratio), for the forward and for the gradients separately.
+
+--hip (needs a GPU): the HIP path's err / e32 on the same cases, merged into the same file under "hip"; the default mode keeps an
+existing "hip" block.
+
+    python tools/cnn_grad_accuracy.py [--draws 8] [--hip] [--out profiles/cnn_grad_accuracy.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import cnn_ref                     # noqa: E402
+import cnn_train_cases as cc       # noqa: E402
+
+
+def spread(errs, norm):
+    med = float(np.median(errs))
+    return {"norm": norm, "plain_err": errs[0], "median_err": med, "max_err": max(errs), "max_over_median": max(errs) / med if med > 0 else 0.0}
+
+
+def ensemble(draws):
+    cases, largest = {}, {"forward": 0.0, "gradients": 0.0}
+    for kind, B, L in cc.GRAD_CASES:
+        spec, w, x, g = cc.grad_case(kind, B, L)
+        pre = {}
+        f64, g64 = cnn_ref.gradients(x, spec, w, g, torch.float64, pre=pre)
+        masks = {k: v > 0 for k, v in pre.items()}
+        _, m64 = cnn_ref.forward(x, spec, w, torch.float64)
+        seeds = [None] + [100 + d for d in range(draws)]
+        fwd = [cnn_ref.forward(x, spec, w, torch.float32, draw=s) for s in seeds]
+        grd = [cnn_ref.gradients(x, spec, w, g, torch.float32, draw=s, masks=masks)[1] for s in seeds]
+        forward = {"features": spread([float(np.linalg.norm(m[0] - f64)) for m in fwd], float(np.linalg.norm(f64)))}
+        for site in m64:
+            for i, leaf in enumerate(("mean", "var")):
+                forward["%s %s" % (site, leaf)] = spread([float(np.linalg.norm(m[1][site][i] - m64[site][i])) for m in fwd],
+                                                         float(np.linalg.norm(m64[site][i])))
+        gradients = {name: spread([float(np.linalg.norm(m[name] - g64[name])) for m in grd], float(np.linalg.norm(g64[name]))) for name in g64}
+        label = "%s B%d L%d" % (kind, B, L)
+        cases[label] = {"forward": forward, "gradients": gradients}
+        for part, rows in (("forward", forward), ("gradients", gradients)):
+            largest[part] = max(largest[part], max(r["max_over_median"] for r in rows.values()))
+        print(label, "largest max/median: forward %.3g, gradients %.3g" % (max(r["max_over_median"] for r in forward.values()),
+                                                                          max(r["max_over_median"] for r in gradients.values())), flush=True)
+    return {"method": "float32 realisations of tests/cnn_ref.py (plain + %d draws: channel orders of every product, batch order) against "
+                      "float64; gradients under fixed ReLU masks (signs of the float64 pre-activations); per tensor the largest member "
+                      "error over the median member's" % draws,
+            "draws": draws, "largest_max_over_median": largest,
+            "factor": {k: max(4.0, 1.5 * v) for k, v in largest.items()}, "cases": cases}
+
+
+def hip(factor):
+    out, worst = {}, 0.0
+    for kind, B, L in cc.GRAD_CASES:
+        spec, w, x, g = cc.grad_case(kind, B, L)
+        fea, mom, dp, gu, masks = cc.hip_run(spec, w, x, g)
+        label = "%s B%d L%d" % (kind, B, L)
+        rows = dict(cc.forward_rows(spec, w, x, fea, mom, factor["forward"]))
+        rows.update(cc.gradient_rows(spec, w, x, dp, gu, masks, factor["gradients"], label))
+        out[label] = {k: {"err_over_e32": r["ratio"], "err_rel": r["err_rel"], "e32_rel": r["e32_rel"], "ok": r["ok"]} for k, r in rows.items()}
+        worst = max(worst, max(r["ratio"] for r in rows.values() if r["err_rel"] > cc.FLOOR))
+        print(label, "largest err/e32 %.3g" % max(r["ratio"] for r in rows.values()), flush=True)
+    return {"note": "chiron_cnn_train_forward / _backward against the same float64 values, error over the plain float32 run's (e32); gradients "
+                    "under the HIP run's own ReLU masks; measured after the factors were fixed",
+            "largest_err_over_e32_above_the_floor": worst, "cases": out}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--draws", type=int, default=8)
+    ap.add_argument("--hip", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cnn_grad_accuracy.json"))
+    a = ap.parse_args()
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    old = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    if a.hip:
+        if "factor" not in old or not isinstance(old["factor"], dict):
+            raise SystemExit("run the CPU ensemble first: --hip reads its factors from %s" % a.out)
+        old["hip"] = hip(old["factor"])
+        out = old
+    else:
+        out = ensemble(a.draws)
+        if "hip" in old:
+            out["hip"] = old["hip"]
+        print("largest ratios %s -> factors %s" % (out["largest_max_over_median"], out["factor"]))
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
