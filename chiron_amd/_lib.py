@@ -24,6 +24,7 @@ X_ON_DEVICE, WANT_PROB, WANT_LOGITS, NO_DECODE_COPY, COMPACT_DECODE = 1, 2, 4, 8
 KERNAL_GLUE, KERNAL_STICK, KERNAL_SIMPLE = 1, 2, 3
 CTC_WANT_GRAD, CTC_TRUSTED = 1, 2
 CTC_MAX_T, CTC_MAX_LABEL = 8192, 1 << 24
+ALIGN_MAX_LEN, ALIGN_BAND0, ALIGN_THREADS, ALIGN_LDS_SLOTS, ALIGN_MAX_GROUPS = 1 << 17, 256, 256, 4096, 2048
 
 
 class ResBlock(C.Structure):
@@ -134,6 +135,9 @@ SYMBOLS = [
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("chiron_cnn_train_backward", C.c_int, [C.c_int32, C.POINTER(ModelDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_align_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    ("chiron_align_pairs", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     ("chiron_last_error", C.c_char_p, []),
     ("chiron_device_pci_bus_id", C.c_int, [C.c_int32, C.c_char_p, C.c_size_t]),
     ("chiron_abi_version", C.c_int32, []),

@@ -319,4 +319,28 @@ void launch_edit(const EditParams& p, hipStream_t stream);
 chiron_status ctc_check_rows(const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int batch, int T, int Lmax);
 chiron_status ctc_sizes(int64_t batch, int64_t T, int64_t Lmax, uint32_t flags, int* S_ws, size_t* bytes);
 
+// ---------------------------------------------------------------------------------------------
+// Read-level assessment (assess.hip): banded global alignment with an exactness certificate, one workgroup per pair
+// ---------------------------------------------------------------------------------------------
+struct AlignPair {
+  int64_t start;             // the read's first code in `codes`; the reference follows it directly
+  int32_t n, m;              // read and reference length
+};
+struct AlignParams {
+  const uint8_t* codes;      // packed: read 0, reference 0, read 1, ... (0..3 bases, 4 matches nothing)
+  const AlignPair* pair;     // [pairs]
+  int64_t pairs;
+  int64_t* rows;             // [groups][row_slots] cells of bands wider than CHIRON_ALIGN_LDS_SLOTS, or null when none can be
+  int64_t row_slots;
+  int32_t* out;              // [pairs][3] E, M, accepted band half-width
+};
+// byte offsets of the workspace's parts and its size; CHIRON_ERR_OVERFLOW past what the kernel addresses
+struct AlignLayout {
+  size_t pair, out, codes, rows, bytes;
+  int64_t row_slots;
+  int groups;
+};
+chiron_status align_layout(int64_t pairs, int64_t max_len, AlignLayout* l);
+int launch_align(const AlignParams& p, int groups, hipStream_t stream);  // 0 on success
+
 }  // namespace chiron

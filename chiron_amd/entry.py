@@ -191,6 +191,26 @@ def train(args):
     return train_mod.train_network(args)
 
 
+def assess(args):
+    """Read-level accuracy of called reads against per-read references: assess.assess (global alignment on the GPU, identity,
+    mismatch, insertion and deletion rates).  Writes a JSON report to args.output; exits non-zero when no read found its
+    reference."""
+    import json
+    from . import assess as assess_mod
+    report = assess_mod.assess(args.input, args.reference, strand=args.strand, device_id=args.device)
+    with open(args.output, "w") as f:
+        json.dump(report, f, indent=1)
+    pooled = report["pooled"]
+    print("assess: %d reads paired, %d unpaired; pooled identity %.4f, mismatch %.4f, insertion %.4f, deletion %.4f"
+          % (report["paired"], report["unpaired_count"], pooled["identity"], pooled["mismatch_rate"], pooled["insertion_rate"],
+             pooled["deletion_rate"]))
+    for name in report["unpaired"]:
+        print("assess: no reference for read %s" % name, file=sys.stderr)
+    if report["paired"] == 0:
+        sys.exit("assess: no read under %s found its reference under %s" % (report["input"], report["reference"]))
+    return report
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -300,6 +320,18 @@ def build_parser():
     r.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
                    help="Use seeded synthetic weights when the model folder has no checkpoint data.")
     r.set_defaults(func=train, retrain=False)
+    a = subparsers.add_parser("assess", description="Read-level accuracy of called reads against per-read references: identity, "
+                              "mismatch, insertion and deletion rates from a global alignment on the GPU",
+                              help="Identity and error rates of called reads against their references.")
+    a.add_argument("-i", "--input", required=True, help="Output folder of `call` (its result/ is read), or a fasta/fastq file or folder.")
+    a.add_argument("-r", "--reference", default=None,
+                   help="Folder of <read>_ref.fastq / <read>.fasta / <read>.fastq, or one fasta/fastq file with a record per read "
+                        "(default: the reference/ folder of the `call` output).")
+    a.add_argument("-o", "--output", required=True, help="JSON report path")
+    a.add_argument("--strand", default="forward", choices=["forward", "both"],
+                   help="both: also align against the reverse complement of the reference and keep the better strand.")
+    a.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    a.set_defaults(func=assess)
     return parser
 
 

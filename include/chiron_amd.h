@@ -536,6 +536,41 @@ chiron_status chiron_cnn_train_backward(int32_t device_id, const chiron_model_de
                                         const float* dfeatures, int32_t batch, int32_t segment_len, const void* tape, void* workspace,
                                         float* dparams_out, void* stream);
 
+/* Read-level assessment: global alignment of a basecalled read against the sequence it should have been, unit costs, for the
+ * identity / mismatch / insertion / deletion rates a basecaller is judged by (the arithmetic behind the reference's
+ * utils/assess.sh; mapping against a genome stays outside: references are per-read sequences).  Per pair (read a of n bases,
+ * reference b of m bases) the result is (E, M): E the Levenshtein distance, M the largest number of matching columns over all
+ * alignments of cost E (minimise E, then maximise M).  The operation counts follow without a traceback: mismatches X = n + m - 2M
+ * - E, insertions I = n - M - X (read bases the reference lacks), deletions D = m - M - X.  Codes 0..3 = A, C, G, T (U is T); code
+ * 4 matches nothing, not even itself.  Empty sequences are legal: E = max(n, m), M = 0.
+ *
+ * One workgroup aligns one pair inside a band of diagonals j - i in [min(0, m-n) - w, max(0, m-n) + w], w = CHIRON_ALIGN_BAND0
+ * at first.  A path that leaves the band costs at least 2(w+1) + |m-n|, so a banded result with E <= 2w + 1 + |m-n| is exact in E
+ * and in M; otherwise the workgroup doubles w and repeats, up to the full table.  band_out is the w that was accepted.  The
+ * result is exact, deterministic, and independent of what else is in the batch.
+ *
+ * Workspace (device memory): the packed codes, the per-pair records and results, and -- when a table of 2 * max_len + 1 diagonals
+ * is wider than the CHIRON_ALIGN_LDS_SLOTS the kernel keeps on chip -- one row of 2 * max_len + 2 64-bit cells for each of at most
+ * CHIRON_ALIGN_MAX_GROUPS workgroups.  max_len: the longest sequence of the call (a larger value is fine).  Host-only.
+ * CHIRON_ERR_INVALID: pairs < 0, max_len < 0.  CHIRON_ERR_OVERFLOW: max_len > CHIRON_ALIGN_MAX_LEN or pairs > 2^24; within those
+ * bounds every offset the kernel forms is 64-bit and every count fits 32 bits.                                                  */
+#define CHIRON_ALIGN_MAX_LEN (1 << 17)
+#define CHIRON_ALIGN_BAND0 256
+#define CHIRON_ALIGN_THREADS 256      /* cells of one anti-diagonal a workgroup updates per pass                                  */
+#define CHIRON_ALIGN_LDS_SLOTS 4096   /* widest band (diagonals) whose cells stay in LDS; wider bands use the workspace row        */
+#define CHIRON_ALIGN_MAX_GROUPS 2048  /* workgroups of one launch; pair p runs on workgroup p mod the launch's group count        */
+chiron_status chiron_align_workspace_size(int64_t pairs, int64_t max_len, size_t* bytes);
+
+/* Align `pairs` pairs in one launch.  codes: HOST bytes; pair p's read is codes[read_off[p] .. read_off[p+1]) and its reference
+ * codes[ref_off[p] .. ref_off[p+1]); read_off and ref_off are HOST int64 [pairs + 1], non-negative and non-decreasing (the two
+ * may interleave in any way; typically all reads, then all references).  edit_out, match_out, band_out: HOST int32 [pairs].
+ * workspace: device memory on device_id of chiron_align_workspace_size(pairs, longest sequence) bytes.  flags: 0 (reserved).
+ * Runs on `stream` (a hipStream_t; NULL = the null stream) and synchronises it before returning.  CHIRON_ERR_INVALID for a bad
+ * offset or a code above 4, CHIRON_ERR_OVERFLOW for a sequence longer than CHIRON_ALIGN_MAX_LEN, both before anything is copied
+ * or launched.  pairs == 0 is a no-op.                                                                                         */
+chiron_status chiron_align_pairs(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const int64_t* ref_off, int64_t pairs,
+                                 uint32_t flags, int32_t* edit_out, int32_t* match_out, int32_t* band_out, void* workspace, void* stream);
+
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
 /* What kind of build this library is.  CHIRON_BUILD_TIMING: at least one object was compiled as a timing-only kernel variant
