@@ -343,4 +343,37 @@ struct AlignLayout {
 chiron_status align_layout(int64_t pairs, int64_t max_len, AlignLayout* l);
 int launch_align(const AlignParams& p, int groups, hipStream_t stream);  // 0 on success
 
+// ---------------------------------------------------------------------------------------------
+// CTC forced alignment (ctc_align.hip): banded max-plus recursion with traceback, one workgroup per read
+// ---------------------------------------------------------------------------------------------
+struct LabelRead {
+  int64_t frame0;            // the read's first frame in `scores` (in frames)
+  int64_t label0;            // its first base in `labels`, and its first entry of `start`
+  int64_t bp;                // byte offset of its back-pointers in `bp`: F rows of bp_rowbytes bytes, four 2-bit cells a byte
+  int32_t F, L;
+  int32_t bp_rowbytes;       // row pitch the host sized for: the widest band the read can reach, in bytes
+};
+struct LabelParams {
+  const float* scores;       // [frames][5], class 4 = blank
+  const uint8_t* labels;     // 0..3
+  const LabelRead* read;     // [reads]
+  int64_t reads;
+  uint8_t* bp;
+  double* rows;              // [groups][2][row_slots] recursion rows of bands wider than lds_slots, or null when none can be
+  int64_t row_slots;
+  int32_t lds_slots;         // states of a recursion row the launch keeps in LDS (<= CHIRON_LABEL_LDS_SLOTS)
+  int32_t band0, max_band;
+  int32_t* start;            // [bases]
+  double* score;             // [reads]
+  int32_t* band;             // [reads]
+  int32_t* status;           // [reads]
+};
+// byte offsets of the workspace's parts and its size
+struct LabelLayout {
+  size_t read, scores, labels, start, score, band, status, rows, bp, bytes;
+  int64_t row_slots, frames, bases;
+  int lds_slots, groups;
+};
+int launch_ctc_align(const LabelParams& p, int groups, hipStream_t stream);  // 0 on success
+
 }  // namespace chiron

@@ -211,6 +211,26 @@ def assess(args):
     return report
 
 
+def label(args):
+    """Labels from the model's own logits: label.label (CTC forced alignment of every read's frames to its reference bases on the
+    GPU).  Writes <out>/<read>.signal + <out>/<read>.label, a folder `validate`, `finetune` and `train` take as -i, and
+    <out>/label_report.json; exits non-zero when no read was labelled."""
+    import logging
+    from . import label as label_mod
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    if args.mode not in ("dna", "rna"):
+        raise ValueError("--mode must be dna or rna, not %r" % (args.mode,))
+    report = label_mod.label(args)
+    t = report["totals"]
+    print("label: %d reads written; %d aligned, %d infeasible, %d band exhausted, %d skipped, %d without a reference"
+          % (t["written"], t["aligned"], t["infeasible"], t["band_exhausted"], t["skipped"], report["no_reference_count"]))
+    for name in report["no_reference"]:
+        print("label: no reference for read %s" % name, file=sys.stderr)
+    if t["written"] == 0:
+        sys.exit("label: no read under %s was labelled" % args.input)
+    return report
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -332,6 +352,27 @@ def build_parser():
                    help="both: also align against the reverse complement of the reference and keep the better strand.")
     a.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     a.set_defaults(func=assess)
+    lb = subparsers.add_parser("label", description="Make training labels: CTC forced alignment of each read's frame logits to its "
+                               "reference bases on the GPU, written as .signal + .label pairs",
+                               help="Write .signal/.label training pairs from reads and their references.")
+    lb.add_argument("-i", "--input", required=True, help="Output folder of `call` (its raw/ and reference/ are read), or a folder of .signal files.")
+    lb.add_argument("-r", "--reference", default=None,
+                    help="Folder of <read>_ref.fastq / <read>.fasta / <read>.fastq, or one fasta/fastq file with a record per read "
+                         "(default: the reference/ folder of the `call` output).")
+    lb.add_argument("-o", "--output", required=True, help="Folder the .signal/.label pairs and label_report.json are written to.")
+    lb.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder path")
+    lb.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
+    lb.add_argument("-b", "--batch_size", type=int, default=1100, help="Windows per engine batch.")
+    lb.add_argument("--band", type=int, default=256, help="First half-width of the alignment band, in CTC states; 0: the full table (exact).")
+    lb.add_argument("--max-band", dest="max_band", type=int, default=8192,
+                    help="Largest half-width the doubling may reach before a read is given up (0: unbounded).")
+    lb.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one alignment batch, MiB.")
+    lb.add_argument("--mode", default="dna", help="dna or rna, as for `call` (U in a reference reads as T in either).")
+    lb.add_argument("--dtype", default="fp32", choices=["fp32", "fp16", "fp16-w2", "fp32-split"], help="Engine arithmetic.")
+    lb.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    lb.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
+                    help="Use seeded synthetic weights when the model folder has no checkpoint data.")
+    lb.set_defaults(func=label)
     return parser
 
 

@@ -571,6 +571,63 @@ chiron_status chiron_align_workspace_size(int64_t pairs, int64_t max_len, size_t
 chiron_status chiron_align_pairs(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const int64_t* ref_off, int64_t pairs,
                                  uint32_t flags, int32_t* edit_out, int32_t* match_out, int32_t* band_out, void* workspace, void* stream);
 
+/* CTC forced alignment: given a read's frame scores and the bases it is known to have, the best monotone assignment of frames
+ * to bases (what a resquiggler gives the reference project; here from the model's own logits).  Read r has frames
+ * frame_off[r] .. frame_off[r+1]) of `scores`, float32 [frames, 5] with class 4 = blank, and bases label_off[r] .. label_off[r+1])
+ * of `labels`, codes 0..3.
+ *
+ * States.  For a read with F frames and L bases the states are s = 0..S-1, S = 2L+1.  Odd s = 2j+1 is base j; even s is blank.
+ * Recurrence.  v_0(0) = x_0[blank], v_0(1) = x_0[l_0], every other v_0 is -inf;
+ *     v_t(s) = best(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2)) + (double)x_t[class(s)].
+ * The s-2 predecessor is allowed only when s is odd and base j differs from base j-1 (the CTC repeat rule).  Values are double;
+ * each step is one IEEE add of a float widened to double, so a numpy float64 restatement reproduces the result bit for bit.
+ * Scores are used as given, with no log-softmax: the best path does not change when a constant is added to all five classes of
+ * a frame, so normalising is the caller's business.  score_out is the sum of the given scores along the path.  Scores must be
+ * finite.
+ * Ties.  A later candidate replaces an earlier one only when it is strictly greater; candidates are taken in the order stay,
+ * s-1, s-2; at the end state S-1 is preferred to S-2.
+ * Output.  start_out[label_off[r] + j] is the first frame the path spends in state 2j+1.
+ *
+ * Band.  A pass of half-width w admits, at frame t, the states with |s - c(t)| <= w, c(t) = floor(t (S-1) / max(F-1, 1)) in
+ * 64-bit integers; every other cell is -inf.  The first pass uses w = band0.  A pass is accepted when the end is reachable and
+ * the traced path never sits on a clipped edge (s = c(t)-w > 0 or s = c(t)+w < S-1); otherwise w doubles and the read is redone,
+ * inside the kernel, so a batch is one launch.  A pass with w >= S-1 is the full table and is always accepted.  band0 == 0 means
+ * the full table at once, and band_out is then 0; otherwise band_out is the w of the last pass (band0 for a status-1 read).
+ * max_band > 0 bounds the doubling (CHIRON_ERR_INVALID when it is below band0; ignored with band0 == 0): when the next w would
+ * exceed max_band and is not yet the full table, the read ends with status 2.
+ *
+ * What a banded result is.  An accepted banded path is the best path INSIDE its band; it is not certified to be the global
+ * optimum.  Observed on a CPU prototype of these rules: a read whose bases all occur in its first ninth and whose remaining frames
+ * are noise was accepted at w = 32 with a score below the full-table optimum.  Only band0 = 0 is exact.  On squiggle-like synthetic
+ * inputs (dwell geometric with mean 9, L = 40 and L = 300, band0 4, 16 and 64, final bands 16 to 64) the banded result was
+ * identical to the full table.  Callers filter on the band reached and on the path's mean log-probability per frame.
+ *
+ * status_out: 0 aligned; 1 infeasible, F < L + the number of adjacent equal bases (F = 0 with L > 0 included); 2 band exhausted.
+ * For 1 and 2 the read's start_out entries are -1 and its score_out is -inf.  L = 0 is legal: status 0, the score is the sum of the
+ * blank scores, no start_out entry.
+ *
+ * Host arrays in, host arrays out: scores, frame_off, labels, label_off, start_out [label_off[reads]], score_out, band_out,
+ * status_out [reads] are HOST memory; workspace is device memory on device_id of the size function's bytes for the same offsets,
+ * band0 and max_band.  It holds the copied inputs and results, two recursion rows of doubles per workgroup for bands wider than
+ * CHIRON_LABEL_LDS_SLOTS states, and the 2-bit back-pointer cells of every read at the widest band that read can reach.  Runs on
+ * `stream` (a hipStream_t; NULL = the null stream) and synchronises it before returning.  flags: 0 (reserved).
+ * CHIRON_ERR_INVALID: decreasing or negative offsets, a code above 3, a score that is not finite, band0 < 0, max_band < 0,
+ * 0 < max_band < band0.  CHIRON_ERR_OVERFLOW: a read above CHIRON_LABEL_MAX_FRAMES or CHIRON_LABEL_MAX_BASES, more than 2^24
+ * reads, more than 2^46 bytes of back-pointers.  All of it before anything is copied or launched.  reads == 0 is a no-op (size 0).
+ * One workgroup of CHIRON_LABEL_THREADS per read; read r runs on workgroup r mod the launch's group count; every offset the
+ * kernel forms is 64-bit.  The size function is host-only.                                                                       */
+#define CHIRON_LABEL_MAX_FRAMES (1 << 24)
+#define CHIRON_LABEL_MAX_BASES (1 << 22)
+#define CHIRON_LABEL_THREADS 256
+#define CHIRON_LABEL_LDS_SLOTS 4096   /* widest band (states) whose two recursion rows stay in LDS (64 KB); wider bands use workspace rows */
+#define CHIRON_LABEL_MAX_GROUPS 1024  /* workgroups of one launch                                                                  */
+chiron_status chiron_ctc_align_workspace_size(int64_t reads, const int64_t* frame_off, const int64_t* label_off, int32_t band0,
+                                              int32_t max_band, size_t* bytes);
+chiron_status chiron_ctc_align(int32_t device_id, const float* scores, const int64_t* frame_off, const uint8_t* labels,
+                               const int64_t* label_off, int64_t reads, int32_t band0, int32_t max_band, uint32_t flags,
+                               int32_t* start_out, double* score_out, int32_t* band_out, int32_t* status_out, void* workspace,
+                               void* stream);
+
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
 /* What kind of build this library is.  CHIRON_BUILD_TIMING: at least one object was compiled as a timing-only kernel variant
