@@ -25,6 +25,7 @@ KERNAL_GLUE, KERNAL_STICK, KERNAL_SIMPLE = 1, 2, 3
 CTC_WANT_GRAD, CTC_TRUSTED = 1, 2
 CTC_MAX_T, CTC_MAX_LABEL = 8192, 1 << 24
 ALIGN_MAX_LEN, ALIGN_BAND0, ALIGN_THREADS, ALIGN_LDS_SLOTS, ALIGN_MAX_GROUPS = 1 << 17, 256, 256, 4096, 2048
+INFIX_MAX_READ, INFIX_MAX_WINDOW, INFIX_BAND0, INFIX_THREADS, INFIX_LDS_SLOTS, INFIX_MAX_GROUPS = 1 << 17, (1 << 20) - 1, 256, 256, 4096, 2048
 LABEL_MAX_FRAMES, LABEL_MAX_BASES, LABEL_THREADS, LABEL_LDS_SLOTS, LABEL_MAX_GROUPS = 1 << 24, 1 << 22, 256, 4096, 1024
 
 
@@ -139,6 +140,9 @@ SYMBOLS = [
     ("chiron_align_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     ("chiron_align_pairs", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    ("chiron_align_infix_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    ("chiron_align_infix", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("chiron_ctc_align_workspace_size", C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("chiron_ctc_align", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

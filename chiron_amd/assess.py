@@ -3,8 +3,8 @@
 `chiron call` leaves result/<read>.fastq and, when a fast5 carries one, reference/<read>_ref.fastq (extract.py).  This module
 pairs the two, aligns every pair globally with unit costs on the GPU (chiron_align_pairs, csrc/assess.hip) and reports the
 numbers basecallers are judged by: identity, mismatch, insertion and deletion rates -- the arithmetic the reference project
-leaves to utils/assess.sh (graphmap, samtools, jsa.hts.errorAnalysis).  Mapping against a genome is out of scope: a reference
-here is the per-read sequence.
+leaves to utils/assess.sh (graphmap, samtools, jsa.hts.errorAnalysis).  A reference here is the per-read sequence; with a genome
+instead, `chiron map` (map.py) finds each read's place in it and cuts that sequence out, and `assess -g` does both in one go.
 
 Per pair (read of n bases, reference of m) the kernel returns (E, M): the Levenshtein distance and the largest number of
 matching columns over the alignments of that cost.  The counts follow without a traceback:

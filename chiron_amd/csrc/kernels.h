@@ -344,6 +344,26 @@ chiron_status align_layout(int64_t pairs, int64_t max_len, AlignLayout* l);
 int launch_align(const AlignParams& p, int groups, hipStream_t stream);  // 0 on success
 
 // ---------------------------------------------------------------------------------------------
+// Read mapping (map.hip): banded infix alignment of a read against a genome window, one workgroup per pair
+// ---------------------------------------------------------------------------------------------
+struct InfixParams {
+  const uint8_t* codes;      // packed: read 0, window 0, read 1, ... (an AlignPair each: the window follows its read directly)
+  const AlignPair* pair;     // [pairs]
+  int64_t pairs;
+  int64_t* rows;             // [groups][row_slots] cells of bands wider than CHIRON_INFIX_LDS_SLOTS, or null when none can be
+  int64_t row_slots;
+  int32_t* out;              // [pairs][5] E, M, s, e, accepted band half-width
+  int32_t band0;             // the first half-width; 0: the full table at once
+};
+struct InfixLayout {
+  size_t pair, out, codes, rows, bytes;
+  int64_t row_slots;
+  int groups;
+};
+chiron_status infix_layout(int64_t pairs, int64_t max_read, int64_t max_window, InfixLayout* l);
+int launch_infix(const InfixParams& p, int groups, hipStream_t stream);  // 0 on success
+
+// ---------------------------------------------------------------------------------------------
 // CTC forced alignment (ctc_align.hip): banded max-plus recursion with traceback, one workgroup per read
 // ---------------------------------------------------------------------------------------------
 struct LabelRead {

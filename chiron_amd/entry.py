@@ -197,7 +197,13 @@ def assess(args):
     reference."""
     import json
     from . import assess as assess_mod
-    report = assess_mod.assess(args.input, args.reference, strand=args.strand, device_id=args.device)
+    if getattr(args, "genome", None):             # no per-read references: map against the genome first (map.py)
+        from . import map as map_mod
+        if args.reference:
+            raise ValueError("assess: give the references with -r or a genome with -g, not both")
+        report = map_mod.assess_genome(args.input, args.genome, device_id=args.device)
+    else:
+        report = assess_mod.assess(args.input, args.reference, strand=args.strand, device_id=args.device)
     with open(args.output, "w") as f:
         json.dump(report, f, indent=1)
     pooled = report["pooled"]
@@ -207,7 +213,24 @@ def assess(args):
     for name in report["unpaired"]:
         print("assess: no reference for read %s" % name, file=sys.stderr)
     if report["paired"] == 0:
-        sys.exit("assess: no read under %s found its reference under %s" % (report["input"], report["reference"]))
+        sys.exit("assess: no read under %s found its reference under %s" % (report["input"], report["reference"] or args.genome))
+    return report
+
+
+def map_reads(args):
+    """Place called reads in a genome: map.map_command (k-mer votes on the host, exact infix alignment on the GPU).  Writes
+    <out>/reference/<read>_ref.fasta (what `assess -r` and `label -r` take), <out>/mapped.paf and <out>/map_report.json; exits
+    non-zero when no read mapped."""
+    from . import map as map_mod
+    report = map_mod.map_command(args.input, args.genome, args.output, min_votes=args.min_votes, max_occ=args.max_occ, band=args.band,
+                                 workspace_mb=args.workspace_mb, device_id=args.device)
+    t = report["totals"]
+    print("map: %d reads; %d mapped, %d unmapped, %d at a window edge; identity of the mapped reads %.4f"
+          % (t["reads"], t["mapped"], t["unmapped"], t["edge"], t["identity"]))
+    for name in report["unmapped"]:
+        print("map: read %s did not map" % name, file=sys.stderr)
+    if t["mapped"] == 0:
+        sys.exit("map: no read under %s mapped to %s" % (args.input, args.genome))
     return report
 
 
@@ -220,6 +243,13 @@ def label(args):
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if args.mode not in ("dna", "rna"):
         raise ValueError("--mode must be dna or rna, not %r" % (args.mode,))
+    if getattr(args, "genome", None):             # no per-read references: cut them out of the genome first (map.py)
+        from . import assess as assess_mod, map as map_mod
+        if args.reference:
+            raise ValueError("label: give the references with -r or a genome with -g, not both")
+        mapped = map_mod.map_reads(assess_mod.load_reads(args.input), map_mod.load_genome(args.genome), device_id=args.device)
+        args.reference = path.join(args.output, "reference")
+        map_mod.write_references(args.reference, mapped["references"])
     report = label_mod.label(args)
     t = report["totals"]
     print("label: %d reads written; %d aligned, %d infeasible, %d band exhausted, %d skipped, %d without a reference"
@@ -347,6 +377,8 @@ def build_parser():
     a.add_argument("-r", "--reference", default=None,
                    help="Folder of <read>_ref.fastq / <read>.fasta / <read>.fastq, or one fasta/fastq file with a record per read "
                         "(default: the reference/ folder of the `call` output).")
+    a.add_argument("-g", "--genome", default=None,
+                   help="A genome FASTA instead of -r: every read is mapped first (as `map` does) and assessed against the stretch it covers.")
     a.add_argument("-o", "--output", required=True, help="JSON report path")
     a.add_argument("--strand", default="forward", choices=["forward", "both"],
                    help="both: also align against the reverse complement of the reference and keep the better strand.")
@@ -359,6 +391,9 @@ def build_parser():
     lb.add_argument("-r", "--reference", default=None,
                     help="Folder of <read>_ref.fastq / <read>.fasta / <read>.fastq, or one fasta/fastq file with a record per read "
                          "(default: the reference/ folder of the `call` output).")
+    lb.add_argument("-g", "--genome", default=None,
+                    help="A genome FASTA instead of -r: the called reads of -i (its result/) are mapped first (as `map` does) and the "
+                         "stretches they cover are written to <output>/reference/ and used as the references.")
     lb.add_argument("-o", "--output", required=True, help="Folder the .signal/.label pairs and label_report.json are written to.")
     lb.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder path")
     lb.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
@@ -373,6 +408,18 @@ def build_parser():
     lb.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
                     help="Use seeded synthetic weights when the model folder has no checkpoint data.")
     lb.set_defaults(func=label)
+    mp = subparsers.add_parser("map", description="Place called reads in a genome: k-mer votes on the host, exact infix alignment of "
+                               "each read against its candidate window on the GPU",
+                               help="Map called reads to a genome and cut out the per-read references.")
+    mp.add_argument("-i", "--input", required=True, help="Output folder of `call` (its result/ is read), or a fasta/fastq file or folder.")
+    mp.add_argument("-g", "--genome", required=True, help="Genome FASTA, one or many contigs.")
+    mp.add_argument("-o", "--output", required=True, help="Folder reference/<read>_ref.fasta, mapped.paf and map_report.json are written to.")
+    mp.add_argument("--min-votes", dest="min_votes", type=int, default=4, help="Fewest seed votes a read needs to be aligned at all.")
+    mp.add_argument("--max-occ", dest="max_occ", type=int, default=64, help="K-mers that occur more often in the genome are not indexed.")
+    mp.add_argument("--band", type=int, default=256, help="First half-width of the alignment band, in diagonals; 0: the full table.")
+    mp.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one alignment batch, MiB.")
+    mp.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    mp.set_defaults(func=map_reads)
     return parser
 
 

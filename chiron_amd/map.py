@@ -1,0 +1,361 @@
+"""Read mapping: where in a genome does each called read lie, and which stretch of it does the read cover?
+
+`assess` and `label` need a reference sequence per read.  A run that has reads and a genome gets them here: seed on the host,
+align on the GPU (chiron_align_infix, csrc/map.hip), cut the covered stretch out.  `chiron map` writes the cut-outs as
+reference/<read>_ref.fasta, which `assess -r` and `label -r` take unchanged, a PAF file and a JSON report.
+
+Seeding is host-side numpy, deterministic and shared by the command and the tests, so a difference between the GPU and the
+reference can only come from the kernel:
+  genome   the contigs (assess.read_records, assess.encode) concatenated with runs of code 4 between them; a k-mer that holds a
+           code 4 is never indexed, so none spans two contigs.
+  index    k = 15, 2 bits per base; a stable argsort of the k-mer codes and their positions.  K-mers that occur more than
+           max_occ times are dropped.
+  votes    each read as given and as its reverse complement: every read k-mer is looked up with searchsorted; a hit at genome
+           position g and read position r votes for the diagonal delta = g - r (concatenated coordinates), binned by
+           delta // 256 (floor).  The score of a bin beta that holds a hit is count(beta) + count(beta + 1); the best score wins,
+           ties to forward before reverse, then to the smaller beta.  The candidate delta* is the lower median of the hits of the
+           winning two bins, ordered by (delta, g); the contig is the one that holds that hit's g.  Below min_votes the read is
+           unmapped.  votes_second is the best score of the other strand or of a bin more than n // 256 + 2 away: reported,
+           never acted on (it is no mapping quality -- the two scores count seeds, not alignments).
+  window   [delta* - slack, delta* + n + slack) clipped to the contig, slack = max(256, n // 8).
+  edge     a match that touches a window edge which is not a contig edge (s = 0, or e = m while the contig goes on) may continue
+           outside: the read's slack doubles and it is aligned again in a follow-up launch, at most three times; then `edge`.
+There is no CPU fallback: without the library or a GPU, align_infix raises.
+"""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+
+from . import _lib, assess
+
+K = 15
+BIN = 256
+SEPARATOR = K                           # code-4 bases between two contigs
+MAX_WIDENINGS = 3
+MIN_VOTES, MAX_OCC = 4, 64
+THREADS = _lib.INFIX_THREADS
+LDS_SLOTS = _lib.INFIX_LDS_SLOTS
+BAND0 = _lib.INFIX_BAND0
+MAX_READ, MAX_WINDOW = _lib.INFIX_MAX_READ, _lib.INFIX_MAX_WINDOW
+
+INFIX_DTYPE = np.dtype([("edit", np.int32), ("match", np.int32), ("start", np.int32), ("end", np.int32), ("band", np.int32)])
+_LETTERS = np.frombuffer(b"ACGTN", dtype=np.uint8)
+
+
+def decode(codes):
+    return _LETTERS[codes].tobytes().decode("ascii")
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the kernel
+# ----------------------------------------------------------------------------------------------------------------------------
+def workspace_size(pairs, max_read, max_window):
+    n = C.c_size_t()
+    _lib.check(_lib.load().chiron_align_infix_workspace_size(pairs, max_read, max_window, C.byref(n)))
+    return int(n.value)
+
+
+def align_infix(reads, windows, band0=BAND0, device_id=0):
+    """Align reads[p] against the best substring of windows[p] (str, bytes or uint8 code arrays) on the GPU, all pairs in one
+    launch.  -> structured array (INFIX_DTYPE): edit, match, start, end (offsets into the window), band."""
+    if len(reads) != len(windows):
+        raise ValueError("%d reads against %d windows" % (len(reads), len(windows)))
+    pairs = len(reads)
+    out = np.zeros(pairs, dtype=INFIX_DTYPE)
+    if pairs == 0:
+        return out
+    a = [assess.encode(s) for s in reads]
+    b = [assess.encode(s) for s in windows]
+    codes = np.ascontiguousarray(np.concatenate(a + b + [np.zeros(1, np.uint8)]))
+    lens_a = np.array([len(s) for s in a], dtype=np.int64)
+    lens_b = np.array([len(s) for s in b], dtype=np.int64)
+    read_off = np.concatenate([[0], np.cumsum(lens_a)]).astype(np.int64)
+    win_off = (read_off[-1] + np.concatenate([[0], np.cumsum(lens_b)])).astype(np.int64)
+    import torch                                  # before the library loads: its ROCm runtime has to come up first (_lib.py)
+    nbytes = workspace_size(pairs, int(lens_a.max()), int(lens_b.max()))   # raises CHIRON_ERR_OVERFLOW before the GPU is touched
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise RuntimeError("chiron_amd.map.align_infix needs a GPU: the alignment has no CPU fallback")
+    dev = torch.device("cuda", device_id)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    res = [np.zeros(pairs, dtype=np.int32) for _ in range(5)]
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(lib.chiron_align_infix(device_id, codes.ctypes.data, read_off.ctypes.data, win_off.ctypes.data, pairs, band0, 0,
+                                      res[0].ctypes.data, res[1].ctypes.data, res[2].ctypes.data, res[3].ctypes.data,
+                                      res[4].ctypes.data, ws.data_ptr(), C.c_void_p(stream.cuda_stream)))
+    del ws
+    out["edit"], out["match"], out["start"], out["end"], out["band"] = res
+    return out
+
+
+def plan_batches(read_lens, win_lens, budget_bytes):
+    """Consecutive pairs grouped so that each group's workspace stays within the budget (a single pair always forms a group)."""
+    batches, cur, mr, mw = [], [], 0, 0
+    for i, (n, m) in enumerate(zip(read_lens, win_lens)):
+        nr, nw = max(mr, n), max(mw, m)
+        if cur and workspace_size(len(cur) + 1, nr, nw) > budget_bytes:
+            batches.append(cur)
+            cur, nr, nw = [], n, m
+        cur.append(i)
+        mr, mw = nr, nw
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def align_in_batches(reads, windows, band0=BAND0, workspace_mb=4096, device_id=0):
+    import torch  # noqa: F401  before plan_batches loads the library: torch's ROCm runtime has to come up first (_lib.py)
+    out = np.zeros(len(reads), dtype=INFIX_DTYPE)
+    for batch in plan_batches([len(r) for r in reads], [len(w) for w in windows], workspace_mb << 20):
+        out[batch] = align_infix([reads[i] for i in batch], [windows[i] for i in batch], band0, device_id)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# genome, index, votes
+# ----------------------------------------------------------------------------------------------------------------------------
+class Genome:
+    """Contigs concatenated into one code array, SEPARATOR code-4 bases between neighbours."""
+
+    def __init__(self, records):
+        self.names = [name for name, _ in records]
+        seqs = [assess.encode(seq) for _, seq in records]
+        self.lengths = np.array([len(s) for s in seqs], dtype=np.int64)
+        self.starts = np.zeros(len(seqs), dtype=np.int64)
+        parts, at = [], 0
+        for c, s in enumerate(seqs):
+            if c:
+                parts.append(np.full(SEPARATOR, 4, np.uint8))
+                at += SEPARATOR
+            self.starts[c] = at
+            parts.append(s)
+            at += len(s)
+        self.codes = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+
+    def contig_of(self, g):
+        """The contig that holds concatenated position g (a separator position counts to the contig before it)."""
+        return int(np.searchsorted(self.starts, g, side="right") - 1)
+
+
+def load_genome(path):
+    records = assess.read_records(path)
+    if not records:
+        raise ValueError("%s holds no sequence" % path)
+    return Genome(records)
+
+
+def kmers(codes, k=K):
+    """(k-mer codes, positions) of every k-mer of `codes` that holds no code above 3: 2 bits per base, first base highest."""
+    n = len(codes) - k + 1
+    if n <= 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    bad = np.concatenate([[0], np.cumsum(codes > 3)])
+    ok = (bad[k:] - bad[:-k]) == 0
+    val = np.zeros(n, dtype=np.int64)
+    c = codes.astype(np.int64) & 3
+    for t in range(k):
+        val = (val << 2) | c[t:t + n]
+    pos = np.nonzero(ok)[0].astype(np.int64)
+    return val[pos], pos
+
+
+def build_index(codes, k=K, max_occ=MAX_OCC):
+    """-> (sorted k-mer codes, their genome positions); equal k-mers keep their positions in rising order (stable sort)."""
+    val, pos = kmers(codes, k)
+    order = np.argsort(val, kind="stable")
+    val, pos = val[order], pos[order]
+    if len(val):
+        first = np.searchsorted(val, val, side="left")
+        last = np.searchsorted(val, val, side="right")
+        keep = (last - first) <= max_occ
+        val, pos = val[keep], pos[keep]
+    return val, pos
+
+
+def hits(index, read_codes, k=K):
+    """(delta, g) of every seed hit of the read against the index."""
+    idx_val, idx_pos = index
+    rv, rp = kmers(read_codes, k)
+    lo = np.searchsorted(idx_val, rv, side="left")
+    cnt = np.searchsorted(idx_val, rv, side="right") - lo
+    total = int(cnt.sum())
+    if total == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    which = np.repeat(np.arange(len(rv)), cnt)
+    within = np.arange(total) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    g = idx_pos[lo[which] + within]
+    return g - rp[which], g
+
+
+def bin_scores(delta):
+    """-> (bins that hold a hit, rising; score of each = its count + the count of the next bin up)."""
+    bins, cnt = np.unique(delta // BIN, return_counts=True)          # floor division: negative diagonals bin downwards
+    score = cnt.copy()
+    if len(bins) > 1:
+        nxt = bins[1:] == bins[:-1] + 1
+        score[:-1] += np.where(nxt, cnt[1:], 0)
+    return bins, score
+
+
+def vote(index, read_codes, k=K):
+    """The seeding decision for one read.  -> dict(votes, votes_second, strand, delta, g) -- delta and g None without a hit."""
+    n = len(read_codes)
+    per = []
+    for strand, codes in (("forward", read_codes), ("reverse", assess.reverse_complement(read_codes))):
+        delta, g = hits(index, codes, k)
+        bins, score = bin_scores(delta) if len(delta) else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+        per.append((strand, delta, g, bins, score))
+    best = [int(p[4].max()) if len(p[4]) else 0 for p in per]
+    w = 1 if best[1] > best[0] else 0                                   # forward wins a tie
+    strand, delta, g, bins, score = per[w]
+    out = {"votes": best[w], "votes_second": best[1 - w], "strand": strand, "delta": None, "g": None}
+    if best[w] == 0:
+        return out
+    beta = int(bins[int(np.argmax(score))])                              # the first maximum: the smaller beta
+    far = np.abs(bins - beta) > n // BIN + 2
+    if far.any():
+        out["votes_second"] = max(out["votes_second"], int(score[far].max()))
+    b = delta // BIN
+    sel = np.nonzero((b == beta) | (b == beta + 1))[0]
+    order = np.lexsort((g[sel], delta[sel]))
+    mid = sel[order[(len(sel) - 1) // 2]]
+    out["delta"], out["g"] = int(delta[mid]), int(g[mid])
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# the pipeline
+# ----------------------------------------------------------------------------------------------------------------------------
+def window_of(genome, contig, delta, n, slack):
+    """[lo, hi) in concatenated coordinates: [delta - slack, delta + n + slack) clipped to the contig."""
+    c0 = int(genome.starts[contig])
+    c1 = c0 + int(genome.lengths[contig])
+    lo = min(max(delta - slack, c0), c1)
+    hi = max(min(delta + n + slack, c1), lo)
+    return lo, hi
+
+
+def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0, aligner=None,
+              seeds=None, index=None):
+    """Map {name: sequence} against a Genome.  aligner(reads, windows, band0) -> INFIX_DTYPE rows replaces the GPU kernel
+    (the tests' reference pipeline); seeds {name: dict(strand, delta, contig)} replaces the voting for those reads (a test
+    hook).  -> dict(reads=[per-read records, name order], references={name: cut-out in the read's orientation}, totals,
+    unmapped=[names])."""
+    if aligner is None:
+        def aligner(rs, ws, band0):
+            return align_in_batches(rs, ws, band0, workspace_mb, device_id)
+    if index is None:
+        index = build_index(genome.codes, K, max_occ)
+    recs, todo = {}, []
+    for name in sorted(reads):
+        codes = assess.encode(reads[name])
+        n = len(codes)
+        rec = {"name": name, "read_len": n, "contig": None, "start": None, "end": None, "strand": None, "edit": None, "match": None,
+               "mismatch": None, "insertion": None, "deletion": None, "identity": None, "votes": 0, "votes_second": 0, "band": None,
+               "widenings": 0, "status": "unmapped"}
+        recs[name] = rec
+        if seeds is not None and name in seeds:
+            sd = seeds[name]
+            strand, delta, contig = sd["strand"], int(sd["delta"]), int(sd["contig"])
+        else:
+            v = vote(index, codes)
+            rec["votes"], rec["votes_second"] = v["votes"], v["votes_second"]
+            if v["votes"] < min_votes or v["delta"] is None:
+                continue
+            strand, delta, contig = v["strand"], v["delta"], genome.contig_of(v["g"])
+        rec["strand"], rec["contig"] = strand, genome.names[contig]
+        todo.append({"rec": rec, "codes": codes if strand == "forward" else assess.reverse_complement(codes), "delta": delta,
+                     "contig": contig, "slack": max(BIN, n // 8)})
+    references = {}
+    while todo:
+        spans = [window_of(genome, t["contig"], t["delta"], len(t["codes"]), t["slack"]) for t in todo]
+        got = aligner([t["codes"] for t in todo], [genome.codes[lo:hi] for lo, hi in spans], band)
+        again = []
+        for t, (lo, hi), r in zip(todo, spans, got):
+            rec = t["rec"]
+            c0 = int(genome.starts[t["contig"]])
+            c1 = c0 + int(genome.lengths[t["contig"]])
+            s, e, n = int(r["start"]), int(r["end"]), len(t["codes"])
+            touches = (s == 0 and lo > c0) or (e == hi - lo and hi < c1)
+            if touches and rec["widenings"] < MAX_WIDENINGS:
+                rec["widenings"] += 1
+                t["slack"] *= 2
+                again.append(t)
+                continue
+            E, M = int(r["edit"]), int(r["match"])
+            x, i, d = assess.counts(n, e - s, E, M)
+            rec.update({"start": lo + s - c0, "end": lo + e - c0, "edit": E, "match": M, "mismatch": x, "insertion": i, "deletion": d,
+                        "band": int(r["band"]), "status": "edge" if touches else "mapped"})
+            rec.update(assess.rates(M, x, i, d))
+            if not touches:
+                cut = genome.codes[lo + s:lo + e]
+                references[rec["name"]] = decode(cut if rec["strand"] == "forward" else assess.reverse_complement(cut))
+        todo = again
+    per_read = [recs[name] for name in sorted(recs)]
+    totals = {st: sum(1 for r in per_read if r["status"] == st) for st in ("mapped", "unmapped", "edge")}
+    totals["reads"] = len(per_read)
+    for key in ("edit", "match", "mismatch", "insertion", "deletion"):
+        totals[key] = int(sum(r[key] for r in per_read if r["status"] == "mapped"))
+    totals.update(assess.rates(totals["match"], totals["mismatch"], totals["insertion"], totals["deletion"]))
+    return {"reads": per_read, "references": references, "totals": totals,
+            "unmapped": [r["name"] for r in per_read if r["status"] == "unmapped"]}
+
+
+def paf_lines(result, genome):
+    """The twelve PAF columns of every mapped read: the whole read is aligned (query 0 .. n), the residue-match column is M, the
+    block length M + X + I + D, the mapping quality 255 (not available)."""
+    tlen = dict(zip(genome.names, (int(v) for v in genome.lengths)))
+    lines = []
+    for r in result["reads"]:
+        if r["status"] != "mapped":
+            continue
+        block = r["match"] + r["mismatch"] + r["insertion"] + r["deletion"]
+        lines.append("\t".join(str(v) for v in (r["name"], r["read_len"], 0, r["read_len"], "+" if r["strand"] == "forward" else "-",
+                                                 r["contig"], tlen[r["contig"]], r["start"], r["end"], r["match"], block, 255)))
+    return lines
+
+
+def write_references(folder, references):
+    os.makedirs(folder, exist_ok=True)
+    for name, seq in references.items():
+        with open(os.path.join(folder, name + "_ref.fasta"), "w") as f:
+            f.write(">%s\n%s\n" % (name, seq))
+
+
+def write_outputs(out_dir, result, genome, meta=None):
+    """reference/<read>_ref.fasta, mapped.paf and map_report.json under out_dir."""
+    os.makedirs(out_dir, exist_ok=True)
+    write_references(os.path.join(out_dir, "reference"), result["references"])
+    with open(os.path.join(out_dir, "mapped.paf"), "w") as f:
+        f.write("".join(ln + "\n" for ln in paf_lines(result, genome)))
+    report = dict(meta or {})
+    report.update({"totals": result["totals"], "unmapped": result["unmapped"], "reads": result["reads"]})
+    with open(os.path.join(out_dir, "map_report.json"), "w") as f:
+        json.dump(report, f, indent=1)
+    return report
+
+
+def map_command(input_path, genome_path, out_dir, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0):
+    """The `map` command: called reads + genome -> the three outputs; returns the report."""
+    genome = load_genome(genome_path)
+    result = map_reads(assess.load_reads(input_path), genome, min_votes, max_occ, band, workspace_mb, device_id)
+    return write_outputs(out_dir, result, genome, {"input": input_path, "genome": genome_path, "k": K, "min_votes": min_votes,
+                                                    "max_occ": max_occ, "band": band})
+
+
+def assess_genome(input_path, genome_path, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0):
+    """`assess -g`: map, then assess every mapped read against its cut-out (which is in the read's orientation, so the global
+    alignment runs forward); the report's strand, contig, start and end come from the mapping.  Reads that did not map are the
+    report's unpaired reads."""
+    reads = assess.load_reads(input_path)
+    mapped = map_reads(reads, load_genome(genome_path), min_votes, max_occ, band, workspace_mb, device_id)
+    paired, unpaired = assess.pair_reads(reads, mapped["references"])
+    rows = assess.align_pairs([p[1] for p in paired], [p[2] for p in paired], device_id)
+    by = {r["name"]: r for r in mapped["reads"]}
+    report = assess.build_report([p[0] for p in paired], rows, [by[p[0]]["strand"] for p in paired], unpaired,
+                                 {"input": input_path, "genome": genome_path, "reference": None, "strand_mode": "mapped"})
+    for rec in report["reads"]:
+        rec.update({key: by[rec["name"]][key] for key in ("contig", "start", "end")})
+    return report

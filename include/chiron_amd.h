@@ -538,7 +538,7 @@ chiron_status chiron_cnn_train_backward(int32_t device_id, const chiron_model_de
 
 /* Read-level assessment: global alignment of a basecalled read against the sequence it should have been, unit costs, for the
  * identity / mismatch / insertion / deletion rates a basecaller is judged by (the arithmetic behind the reference's
- * utils/assess.sh; mapping against a genome stays outside: references are per-read sequences).  Per pair (read a of n bases,
+ * utils/assess.sh; references are per-read sequences, and chiron_align_infix below cuts them out of a genome).  Per pair (read a of n bases,
  * reference b of m bases) the result is (E, M): E the Levenshtein distance, M the largest number of matching columns over all
  * alignments of cost E (minimise E, then maximise M).  The operation counts follow without a traceback: mismatches X = n + m - 2M
  * - E, insertions I = n - M - X (read bases the reference lacks), deletions D = m - M - X.  Codes 0..3 = A, C, G, T (U is T); code
@@ -570,6 +570,46 @@ chiron_status chiron_align_workspace_size(int64_t pairs, int64_t max_len, size_t
  * or launched.  pairs == 0 is a no-op.                                                                                         */
 chiron_status chiron_align_pairs(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const int64_t* ref_off, int64_t pairs,
                                  uint32_t flags, int32_t* edit_out, int32_t* match_out, int32_t* band_out, void* workspace, void* stream);
+
+/* Read mapping: infix (semi-global) alignment of a read against a genome window, unit costs, same codes as chiron_align_pairs.
+ * Per pair (read a of n bases, window b of m bases), over every substring b[s:e), 0 <= s <= e <= m, and every global alignment
+ * of a against it, the result is the tuple (E, M, s, e) that is smallest in this order: smallest edit cost E, then largest
+ * number of matching columns M, then smallest s, then smallest e.  It is a property of the inputs, not of a tie order inside the
+ * kernel.  Empty inputs are legal: n = 0 gives (0, 0, 0, 0), m = 0 gives (n, 0, 0, 0).  X, I, D of the chosen alignment follow as
+ * for chiron_align_pairs with the reference length e - s.
+ *
+ * One workgroup aligns one pair; a cell carries (E, -M, s) in one 64-bit key E * 2^40 - M * 2^20 + s, which is why a read has at
+ * most CHIRON_INFIX_MAX_READ and a window at most CHIRON_INFIX_MAX_WINDOW bases.  The sweep covers the diagonals j - i in
+ * [min(0, m-n) - w, max(0, m-n) + w], w = band0 at first.  An alignment starts on a diagonal s >= 0 and ends on one <= m - n, and
+ * only a gap changes the diagonal, so one that touches a diagonal outside the band -- one that starts above it included -- costs
+ * at least w + 1: a banded result with E <= w is exact in all four values for the whole window.  (Not the 2w + 1 + |m-n| of
+ * chiron_align_pairs: the ends are free here.)  Otherwise the workgroup doubles w and repeats, up to the full table, which is
+ * always accepted.  band_out is the w that was accepted.  band0 = 0: the full table at once, band_out = 0.  The result is exact,
+ * deterministic, and independent of what else is in the batch.
+ *
+ * Workspace (device memory): the packed codes, the per-pair records and results, and -- when a table of max_read + max_window + 1
+ * diagonals is wider than the CHIRON_INFIX_LDS_SLOTS the kernel keeps on chip -- one row of that many 64-bit cells (plus one) for
+ * each of at most CHIRON_INFIX_MAX_GROUPS workgroups.  max_read, max_window: the longest of the call (larger values are fine).
+ * Host-only.  CHIRON_ERR_INVALID: a negative argument.  CHIRON_ERR_OVERFLOW: max_read > CHIRON_INFIX_MAX_READ, max_window >
+ * CHIRON_INFIX_MAX_WINDOW or pairs > 2^24; within those bounds every offset the kernel forms is 64-bit.                          */
+#define CHIRON_INFIX_MAX_READ (1 << 17)
+#define CHIRON_INFIX_MAX_WINDOW ((1 << 20) - 1)
+#define CHIRON_INFIX_BAND0 256        /* the band0 the `map` command passes                                                       */
+#define CHIRON_INFIX_THREADS 256      /* cells of one anti-diagonal a workgroup updates per pass                                  */
+#define CHIRON_INFIX_LDS_SLOTS 4096   /* widest band (diagonals) whose cells stay in LDS; wider bands use the workspace row        */
+#define CHIRON_INFIX_MAX_GROUPS 2048  /* workgroups of one launch; pair p runs on workgroup p mod the launch's group count        */
+chiron_status chiron_align_infix_workspace_size(int64_t pairs, int64_t max_read, int64_t max_window, size_t* bytes);
+
+/* Align `pairs` pairs in one launch.  codes: HOST bytes; pair p's read is codes[read_off[p] .. read_off[p+1]) and its window
+ * codes[win_off[p] .. win_off[p+1]); read_off and win_off are HOST int64 [pairs + 1], non-negative and non-decreasing.  edit_out,
+ * match_out, start_out, end_out, band_out: HOST int32 [pairs]; start and end are offsets into the pair's window.  workspace:
+ * device memory on device_id of chiron_align_infix_workspace_size(pairs, longest read, longest window) bytes.  flags: 0
+ * (reserved).  Runs on `stream` (a hipStream_t; NULL = the null stream) and synchronises it before returning.
+ * CHIRON_ERR_INVALID for a bad offset, a code above 4 or band0 < 0, CHIRON_ERR_OVERFLOW for a read or window past its limit, all
+ * before anything is copied or launched.  pairs == 0 is a no-op.                                                                */
+chiron_status chiron_align_infix(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const int64_t* win_off, int64_t pairs,
+                                 int32_t band0, uint32_t flags, int32_t* edit_out, int32_t* match_out, int32_t* start_out,
+                                 int32_t* end_out, int32_t* band_out, void* workspace, void* stream);
 
 /* CTC forced alignment: given a read's frame scores and the bases it is known to have, the best monotone assignment of frames
  * to bases (what a resquiggler gives the reference project; here from the model's own logits).  Read r has frames
