@@ -11,7 +11,9 @@ matching columns over the alignments of that cost.  The counts follow without a 
     mismatches X = n + m - 2M - E,  insertions I = n - M - X (read bases the reference lacks),  deletions D = m - M - X,
     identity = M / (M + X + I + D), and the three error rates over the same denominator.
 Bases compare case-insensitively, U is T, and any other character (N included) matches nothing, not even itself.
-There is no CPU fallback: without the library or a GPU, align_pairs raises.
+With `--profile` the alignment itself is computed as well (chiron_align_trace, csrc/trace.hip): the canonical optimal alignment's
+columns, from which cigar() and error_profile() read which substitutions occur and how homopolymers are called.
+There is no CPU fallback: without the library or a GPU, align_pairs and align_ops raise.
 """
 import ctypes as C
 import os
@@ -207,6 +209,163 @@ def align_pairs(reads, refs, device_id=0):
     return out
 
 
+OP_LETTERS = "=XID"                   # the column codes of chiron_align_trace: match, mismatch, insertion (read only), deletion (reference only)
+HP_MAX_RUN, HP_MAX_CALLED = 10, 20    # the homopolymer table's last row and column collect everything beyond them
+
+
+def trace_pair_size(n, m, edit):
+    """(back-pointer bytes, band in diagonals) of one pair, from the library's host-only helper."""
+    nbytes, band = C.c_int64(), C.c_int64()
+    _lib.check(_lib.load().chiron_align_trace_pair_size(n, m, edit, C.byref(nbytes), C.byref(band)))
+    return int(nbytes.value), int(band.value)
+
+
+def trace_workspace_size(pairs, backpointer_bytes, max_len, max_band):
+    n = C.c_size_t()
+    _lib.check(_lib.load().chiron_align_trace_workspace_size(pairs, backpointer_bytes, max_len, max_band, C.byref(n)))
+    return int(n.value)
+
+
+def plan_trace_batches(read_lens, ref_lens, edits, budget_bytes):
+    """Consecutive pairs grouped so that each group's workspace stays within the budget (a single pair always forms a group).
+    -> [(indices, workspace bytes)]; host-only."""
+    batches, cur, cur_bytes, bp, ml, mb = [], [], 0, 0, 0, 0
+    for i, (n, m, e) in enumerate(zip(read_lens, ref_lens, edits)):
+        pb, band = trace_pair_size(int(n), int(m), int(e))
+        nbp, nml, nmb = bp + pb, max(ml, int(n), int(m)), max(mb, band)
+        need = trace_workspace_size(len(cur) + 1, nbp, nml, nmb)
+        if cur and need > budget_bytes:
+            batches.append((cur, cur_bytes))
+            cur, nbp, nml, nmb = [], pb, max(int(n), int(m)), band
+            need = trace_workspace_size(1, nbp, nml, nmb)
+        cur.append(i)
+        cur_bytes, bp, ml, mb = need, nbp, nml, nmb
+    if cur:
+        batches.append((cur, cur_bytes))
+    return batches
+
+
+def trace_pairs(a, b, edit, match, workspace_bytes, device_id=0):
+    """One chiron_align_trace call on code arrays a[p], b[p] with their known (edit, match).  -> ([uint8 op arrays], status)."""
+    pairs = len(a)
+    codes = np.ascontiguousarray(np.concatenate(list(a) + list(b) + [np.zeros(1, np.uint8)]))
+    lens_a = np.array([len(s) for s in a], dtype=np.int64)
+    lens_b = np.array([len(s) for s in b], dtype=np.int64)
+    read_off = np.concatenate([[0], np.cumsum(lens_a)]).astype(np.int64)
+    ref_off = (read_off[-1] + np.concatenate([[0], np.cumsum(lens_b)])).astype(np.int64)
+    edit = np.ascontiguousarray(edit, dtype=np.int32)
+    match = np.ascontiguousarray(match, dtype=np.int32)
+    ops_off = np.concatenate([[0], np.cumsum(edit.astype(np.int64) + match)]).astype(np.int64)
+    ops = np.zeros(max(int(ops_off[-1]), 1), dtype=np.uint8)
+    status = np.zeros(pairs, dtype=np.int32)
+    import torch
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise RuntimeError("chiron_amd.assess.align_ops needs a GPU: the traceback has no CPU fallback")
+    dev = torch.device("cuda", device_id)
+    ws = torch.empty(max(workspace_bytes, 256), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    _lib.check(lib.chiron_align_trace(device_id, codes.ctypes.data, read_off.ctypes.data, ref_off.ctypes.data, pairs, edit.ctypes.data,
+                                      match.ctypes.data, ops_off.ctypes.data, 0, ops.ctypes.data, status.ctypes.data, ws.data_ptr(),
+                                      C.c_void_p(stream.cuda_stream)))
+    del ws
+    return [ops[ops_off[p]:ops_off[p + 1]].copy() for p in range(pairs)], status
+
+
+def align_ops(reads, refs, workspace_mb=4096, device_id=0):
+    """The canonical optimal alignment of reads[p] against refs[p] (str, bytes or uint8 code arrays): a list of uint8 arrays, one
+    byte per column (0 '=', 1 'X', 2 'I', 3 'D').  align_pairs gives (E, M); the pairs are then traced in batches whose
+    workspace stays within workspace_mb (a single pair always forms a batch)."""
+    if len(reads) != len(refs):
+        raise ValueError("%d reads against %d references" % (len(reads), len(refs)))
+    a = [encode(s) for s in reads]
+    b = [encode(s) for s in refs]
+    if not a:
+        return []
+    rows = align_pairs(a, b, device_id)
+    out = [None] * len(a)
+    for batch, nbytes in plan_trace_batches(rows["read_len"], rows["ref_len"], rows["edit"], workspace_mb << 20):
+        ops, status = trace_pairs([a[i] for i in batch], [b[i] for i in batch], rows["edit"][batch], rows["match"][batch], nbytes, device_id)
+        if status.any():
+            raise RuntimeError("chiron_align_trace: pair %d does not have the (E, M) chiron_align_pairs gave it" % batch[int(np.nonzero(status)[0][0])])
+        for i, o in zip(batch, ops):
+            out[i] = o
+    return out
+
+
+def cigar(ops):
+    """Run-length string over =XID of an op array; '*' for an empty alignment."""
+    ops = np.asarray(ops, dtype=np.uint8)
+    if len(ops) == 0:
+        return "*"
+    ends = np.concatenate([np.nonzero(ops[1:] != ops[:-1])[0] + 1, [len(ops)]])
+    starts = np.concatenate([[0], ends[:-1]])
+    return "".join("%d%s" % (e - s, OP_LETTERS[ops[s]]) for s, e in zip(starts, ends))
+
+
+def error_profile(read, ref, ops):
+    """Which errors the canonical alignment `ops` of read against ref holds, as integer tables (nested lists):
+      substitution[r][c]   '=' and 'X' columns with reference base r and read base c, both 0..3 (the diagonal counts matches)
+      other_mismatch       'X' columns with a code 4 on either side
+      insertion[c]         'I' columns by the inserted read code, deletion[c] 'D' columns by the deleted reference code (0..4)
+      homopolymer[L][c]    maximal runs of one base (0..3) of length L in the reference whose called length is c: the number of
+                           read bases equal to the run's base in the run's span, which is the columns after the column of the
+                           previous reference base up to and including the column of the run's last base (the run's own columns
+                           and the insertions directly before and inside it).  L above 10 counts in row 10, c above 20 in column
+                           20; row 0 stays empty."""
+    a, b = encode(read), encode(ref)
+    ops = np.asarray(ops, dtype=np.uint8)
+    on_read, on_ref = ops != 3, ops != 2
+    if int(on_read.sum()) != len(a) or int(on_ref.sum()) != len(b):
+        raise ValueError("the alignment covers %d read and %d reference bases, the sequences have %d and %d"
+                         % (int(on_read.sum()), int(on_ref.sum()), len(a), len(b)))
+    ca = np.full(len(ops), 5, dtype=np.int64)          # the read code of each column, 5 where it has none
+    cb = np.full(len(ops), 5, dtype=np.int64)
+    ca[on_read] = a
+    cb[on_ref] = b
+    sub = np.zeros((4, 4), dtype=np.int64)
+    diag = ops < 2
+    both = diag & (ca < 4) & (cb < 4)
+    np.add.at(sub, (cb[both], ca[both]), 1)
+    hp = np.zeros((HP_MAX_RUN + 1, HP_MAX_CALLED + 1), dtype=np.int64)
+    if len(b):
+        col_of = np.nonzero(on_ref)[0]                  # the column of every reference base
+        cuts = np.nonzero(b[1:] != b[:-1])[0] + 1
+        first = np.concatenate([[0], cuts])
+        last = np.concatenate([cuts, [len(b)]]) - 1
+        called = np.zeros((4, len(ops) + 1), dtype=np.int64)
+        for base in range(4):
+            called[base, 1:] = np.cumsum(ca == base)
+        base = b[first].astype(np.int64)
+        keep = base < 4
+        span_end = col_of[last] + 1
+        span_start = np.where(first > 0, col_of[np.maximum(first - 1, 0)] + 1, 0)
+        c = called[np.minimum(base, 3), span_end] - called[np.minimum(base, 3), span_start]
+        np.add.at(hp, (np.minimum(last - first + 1, HP_MAX_RUN)[keep], np.minimum(c, HP_MAX_CALLED)[keep]), 1)
+    return {"substitution": sub.tolist(), "other_mismatch": int(((ops == 1) & ~both).sum()),
+            "insertion": np.bincount(ca[ops == 2], minlength=5)[:5].tolist(),
+            "deletion": np.bincount(cb[ops == 3], minlength=5)[:5].tolist(), "homopolymer": hp.tolist()}
+
+
+def merge(profiles):
+    """The sum of error profiles, table by table; the empty profile for none."""
+    out = error_profile("", "", np.zeros(0, np.uint8))
+    for prof in profiles:
+        for key, val in prof.items():
+            out[key] = (np.asarray(out[key], dtype=np.int64) + np.asarray(val, dtype=np.int64)).tolist()
+    return out
+
+
+def add_profile(report, reads, refs, workspace_mb=4096, device_id=0):
+    """Trace reads[k] against refs[k] (the pairs of report["reads"], in its order) and add `cigar` per read and the pooled
+    `profile` to the report."""
+    ops = align_ops(reads, refs, workspace_mb, device_id)
+    for rec, o in zip(report["reads"], ops):
+        rec["cigar"] = cigar(o)
+    report["profile"] = merge(error_profile(a, b, o) for a, b, o in zip(reads, refs, ops))
+    return report
+
+
 def choose_strand(fwd, rev):
     """Per pair the better of the forward and the reverse-complement alignment: smaller E, then larger M; forward wins ties.
     -> (chosen rows, ["forward" | "reverse"])."""
@@ -236,8 +395,9 @@ def build_report(names, rows, strands, unpaired, meta=None):
     return report
 
 
-def assess(input_path, reference_path=None, strand="forward", device_id=0):
-    """Pair, align, report.  reference_path None: the `call` output tree's own reference/ folder."""
+def assess(input_path, reference_path=None, strand="forward", device_id=0, profile=False, workspace_mb=4096):
+    """Pair, align, report.  reference_path None: the `call` output tree's own reference/ folder.  profile: also trace every
+    pair (on the strand that won) and add the per-read cigar and the pooled error profile."""
     if strand not in ("forward", "both"):
         raise ValueError("strand must be forward or both, not %r" % (strand,))
     if reference_path is None:
@@ -256,5 +416,8 @@ def assess(input_path, reference_path=None, strand="forward", device_id=0):
     else:
         rows = align_pairs(a, b, device_id)
         strands = ["forward"] * len(a)
-    return build_report(names, rows, strands, unpaired,
-                        {"input": input_path, "reference": reference_path, "strand_mode": strand})
+    report = build_report(names, rows, strands, unpaired,
+                          {"input": input_path, "reference": reference_path, "strand_mode": strand})
+    if profile:
+        add_profile(report, a, [reverse_complement(s) if st == "reverse" else s for s, st in zip(b, strands)], workspace_mb, device_id)
+    return report

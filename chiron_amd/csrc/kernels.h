@@ -396,4 +396,41 @@ struct LabelLayout {
 };
 int launch_ctc_align(const LabelParams& p, int groups, hipStream_t stream);  // 0 on success
 
+// ---------------------------------------------------------------------------------------------
+// Alignment traceback (trace.hip): the canonical optimal alignment of a pair whose (E, M) is known, one workgroup per pair
+// ---------------------------------------------------------------------------------------------
+struct TracePair {
+  int64_t start;             // the read's first code in `codes`; the reference follows it directly
+  int64_t bp;                // byte offset of its back-pointers in `bp`: n + m + 1 rows of rowbytes bytes, four 2-bit cells a byte
+  int64_t ops;               // its first column in `ops`; it has E + M columns
+  int32_t n, m;              // read and reference length
+  int32_t E, M;              // what the caller says the pair's distance and match count are
+  int32_t dlo, dhi;          // the band's diagonals j - i, clipped to the table
+  int32_t rowbytes;          // back-pointer bytes of one anti-diagonal
+  int32_t pad_;
+};
+struct TraceParams {
+  const uint8_t* codes;      // packed: read 0, reference 0, read 1, ...
+  const TracePair* pair;     // [pairs]
+  int64_t pairs;
+  int64_t* rows;             // [groups][row_slots] cells of bands wider than CHIRON_ALIGN_LDS_SLOTS, or null when none is
+  int64_t row_slots;
+  uint8_t* bp;
+  uint8_t* ops;              // one byte per column: 0 =, 1 X, 2 I, 3 D
+  int32_t* status;           // [pairs]
+};
+// one pair's band at the half-width its cost allows, w* = (E - |m-n|) / 2, and the size of its back-pointer table
+struct TraceBand {
+  int32_t dlo, dhi, rowbytes;
+  int64_t width, bytes;
+};
+TraceBand trace_band(int64_t n, int64_t m, int64_t E);
+struct TraceLayout {
+  size_t pair, status, codes, ops, rows, bp, bytes;
+  int64_t row_slots;
+  int groups;
+};
+chiron_status trace_layout(int64_t pairs, int64_t backpointer_bytes, int64_t max_len, int64_t max_band, TraceLayout* l);
+int launch_trace(const TraceParams& p, int groups, hipStream_t stream);  // 0 on success
+
 }  // namespace chiron

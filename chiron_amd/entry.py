@@ -201,9 +201,10 @@ def assess(args):
         from . import map as map_mod
         if args.reference:
             raise ValueError("assess: give the references with -r or a genome with -g, not both")
-        report = map_mod.assess_genome(args.input, args.genome, device_id=args.device)
+        report = map_mod.assess_genome(args.input, args.genome, workspace_mb=args.workspace_mb, device_id=args.device, profile=args.profile)
     else:
-        report = assess_mod.assess(args.input, args.reference, strand=args.strand, device_id=args.device)
+        report = assess_mod.assess(args.input, args.reference, strand=args.strand, device_id=args.device, profile=args.profile,
+                                   workspace_mb=args.workspace_mb)
     with open(args.output, "w") as f:
         json.dump(report, f, indent=1)
     pooled = report["pooled"]
@@ -223,7 +224,7 @@ def map_reads(args):
     non-zero when no read mapped."""
     from . import map as map_mod
     report = map_mod.map_command(args.input, args.genome, args.output, min_votes=args.min_votes, max_occ=args.max_occ, band=args.band,
-                                 workspace_mb=args.workspace_mb, device_id=args.device)
+                                 workspace_mb=args.workspace_mb, device_id=args.device, cigar=args.cigar)
     t = report["totals"]
     print("map: %d reads; %d mapped, %d unmapped, %d at a window edge; identity of the mapped reads %.4f"
           % (t["reads"], t["mapped"], t["unmapped"], t["edge"], t["identity"]))
@@ -382,6 +383,10 @@ def build_parser():
     a.add_argument("-o", "--output", required=True, help="JSON report path")
     a.add_argument("--strand", default="forward", choices=["forward", "both"],
                    help="both: also align against the reverse complement of the reference and keep the better strand.")
+    a.add_argument("--profile", action="store_true",
+                   help="Also trace every pair on the GPU: the report gains each read's CIGAR (over =XID) and the pooled error profile "
+                        "(substitution, insertion, deletion and homopolymer tables).")
+    a.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one traceback batch, MiB.")
     a.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     a.set_defaults(func=assess)
     lb = subparsers.add_parser("label", description="Make training labels: CTC forced alignment of each read's frame logits to its "
@@ -418,6 +423,9 @@ def build_parser():
     mp.add_argument("--max-occ", dest="max_occ", type=int, default=64, help="K-mers that occur more often in the genome are not indexed.")
     mp.add_argument("--band", type=int, default=256, help="First half-width of the alignment band, in diagonals; 0: the full table.")
     mp.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one alignment batch, MiB.")
+    mp.add_argument("--cigar", action="store_true",
+                    help="Also trace every mapped read against the stretch it covers, in genome orientation: mapped.paf gains a cg:Z: "
+                         "tag and mapped.sam is written.")
     mp.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     mp.set_defaults(func=map_reads)
     return parser

@@ -2,7 +2,9 @@
 
 `assess` and `label` need a reference sequence per read.  A run that has reads and a genome gets them here: seed on the host,
 align on the GPU (chiron_align_infix, csrc/map.hip), cut the covered stretch out.  `chiron map` writes the cut-outs as
-reference/<read>_ref.fasta, which `assess -r` and `label -r` take unchanged, a PAF file and a JSON report.
+reference/<read>_ref.fasta, which `assess -r` and `label -r` take unchanged, a PAF file and a JSON report.  With `--cigar` every
+mapped read is also traced against the stretch it covers (assess.align_ops, csrc/trace.hip), in genome orientation: the PAF lines
+gain a cg:Z: tag and mapped.sam is written.
 
 Seeding is host-side numpy, deterministic and shared by the command and the tests, so a difference between the GPU and the
 reference can only come from the kernel:
@@ -303,17 +305,54 @@ def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, w
             "unmapped": [r["name"] for r in per_read if r["status"] == "unmapped"]}
 
 
+def add_cigars(result, reads, genome, workspace_mb=4096, device_id=0, tracer=None):
+    """Trace every mapped read of a map_reads result against genome[start : end) of its contig on the forward genome strand -- a
+    reverse-strand read as its reverse complement, the orientation map_reads aligned it in -- and record the CIGAR (over =XID, in
+    genome coordinates, gaps left-aligned there) as the record's `cigar`.  tracer(reads, refs) -> op arrays replaces
+    assess.align_ops (the tests' reference)."""
+    if tracer is None:
+        def tracer(rs, fs):
+            return assess.align_ops(rs, fs, workspace_mb, device_id)
+    contig = {name: c for c, name in enumerate(genome.names)}
+    recs = [r for r in result["reads"] if r["status"] == "mapped"]
+    seqs, cuts = [], []
+    for r in recs:
+        codes = assess.encode(reads[r["name"]])
+        c0 = int(genome.starts[contig[r["contig"]]])
+        seqs.append(codes if r["strand"] == "forward" else assess.reverse_complement(codes))
+        cuts.append(genome.codes[c0 + r["start"]:c0 + r["end"]])
+    for r, ops in zip(recs, tracer(seqs, cuts) if recs else []):
+        r["cigar"] = assess.cigar(ops)
+    return result
+
+
+def sam_lines(result, reads, genome):
+    """@HD, @SQ per contig, then one line per mapped read that carries a `cigar` (add_cigars): FLAG 0 or 16, POS 1-based, MAPQ 255
+    (not available), the CIGAR over =XID, SEQ in genome orientation, QUAL *, and NM:i:E."""
+    lines = ["@HD\tVN:1.6\tSO:unknown"] + ["@SQ\tSN:%s\tLN:%d" % (name, int(n)) for name, n in zip(genome.names, genome.lengths)]
+    for r in result["reads"]:
+        if r["status"] != "mapped" or "cigar" not in r:
+            continue
+        codes = assess.encode(reads[r["name"]])
+        seq = decode(codes if r["strand"] == "forward" else assess.reverse_complement(codes))
+        lines.append("\t".join(str(v) for v in (r["name"], 0 if r["strand"] == "forward" else 16, r["contig"], r["start"] + 1, 255, r["cigar"],
+                                                 "*", 0, 0, seq or "*", "*", "NM:i:%d" % r["edit"])))
+    return lines
+
+
 def paf_lines(result, genome):
     """The twelve PAF columns of every mapped read: the whole read is aligned (query 0 .. n), the residue-match column is M, the
-    block length M + X + I + D, the mapping quality 255 (not available)."""
+    block length M + X + I + D, the mapping quality 255 (not available).  A record that carries a `cigar` (add_cigars) gets a
+    cg:Z: tag after them."""
     tlen = dict(zip(genome.names, (int(v) for v in genome.lengths)))
     lines = []
     for r in result["reads"]:
         if r["status"] != "mapped":
             continue
         block = r["match"] + r["mismatch"] + r["insertion"] + r["deletion"]
-        lines.append("\t".join(str(v) for v in (r["name"], r["read_len"], 0, r["read_len"], "+" if r["strand"] == "forward" else "-",
-                                                 r["contig"], tlen[r["contig"]], r["start"], r["end"], r["match"], block, 255)))
+        cols = (r["name"], r["read_len"], 0, r["read_len"], "+" if r["strand"] == "forward" else "-", r["contig"], tlen[r["contig"]],
+                r["start"], r["end"], r["match"], block, 255) + (("cg:Z:" + r["cigar"],) if "cigar" in r else ())
+        lines.append("\t".join(str(v) for v in cols))
     return lines
 
 
@@ -324,12 +363,16 @@ def write_references(folder, references):
             f.write(">%s\n%s\n" % (name, seq))
 
 
-def write_outputs(out_dir, result, genome, meta=None):
-    """reference/<read>_ref.fasta, mapped.paf and map_report.json under out_dir."""
+def write_outputs(out_dir, result, genome, meta=None, reads=None):
+    """reference/<read>_ref.fasta, mapped.paf and map_report.json under out_dir; with reads (a result that went through
+    add_cigars) mapped.sam as well."""
     os.makedirs(out_dir, exist_ok=True)
     write_references(os.path.join(out_dir, "reference"), result["references"])
     with open(os.path.join(out_dir, "mapped.paf"), "w") as f:
         f.write("".join(ln + "\n" for ln in paf_lines(result, genome)))
+    if reads is not None:
+        with open(os.path.join(out_dir, "mapped.sam"), "w") as f:
+            f.write("".join(ln + "\n" for ln in sam_lines(result, reads, genome)))
     report = dict(meta or {})
     report.update({"totals": result["totals"], "unmapped": result["unmapped"], "reads": result["reads"]})
     with open(os.path.join(out_dir, "map_report.json"), "w") as f:
@@ -337,18 +380,25 @@ def write_outputs(out_dir, result, genome, meta=None):
     return report
 
 
-def map_command(input_path, genome_path, out_dir, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0):
-    """The `map` command: called reads + genome -> the three outputs; returns the report."""
+def map_command(input_path, genome_path, out_dir, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0,
+                cigar=False):
+    """The `map` command: called reads + genome -> the three outputs (with cigar: traced, and mapped.sam too); returns the report."""
     genome = load_genome(genome_path)
-    result = map_reads(assess.load_reads(input_path), genome, min_votes, max_occ, band, workspace_mb, device_id)
-    return write_outputs(out_dir, result, genome, {"input": input_path, "genome": genome_path, "k": K, "min_votes": min_votes,
-                                                    "max_occ": max_occ, "band": band})
+    reads = assess.load_reads(input_path)
+    result = map_reads(reads, genome, min_votes, max_occ, band, workspace_mb, device_id)
+    meta = {"input": input_path, "genome": genome_path, "k": K, "min_votes": min_votes, "max_occ": max_occ, "band": band}
+    if not cigar:
+        return write_outputs(out_dir, result, genome, meta)
+    add_cigars(result, reads, genome, workspace_mb, device_id)
+    return write_outputs(out_dir, result, genome, dict(meta, cigar=True), reads)
 
 
-def assess_genome(input_path, genome_path, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0):
+def assess_genome(input_path, genome_path, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0,
+                  profile=False):
     """`assess -g`: map, then assess every mapped read against its cut-out (which is in the read's orientation, so the global
     alignment runs forward); the report's strand, contig, start and end come from the mapping.  Reads that did not map are the
-    report's unpaired reads."""
+    report's unpaired reads.  profile: the per-read cigar and the pooled error profile as well, in the read's orientation (not the
+    genome's, unlike `map --cigar`); the report's profile_orientation says so."""
     reads = assess.load_reads(input_path)
     mapped = map_reads(reads, load_genome(genome_path), min_votes, max_occ, band, workspace_mb, device_id)
     paired, unpaired = assess.pair_reads(reads, mapped["references"])
@@ -358,4 +408,7 @@ def assess_genome(input_path, genome_path, min_votes=MIN_VOTES, max_occ=MAX_OCC,
                                  {"input": input_path, "genome": genome_path, "reference": None, "strand_mode": "mapped"})
     for rec in report["reads"]:
         rec.update({key: by[rec["name"]][key] for key in ("contig", "start", "end")})
+    if profile:
+        report["profile_orientation"] = "read"
+        assess.add_profile(report, [assess.encode(p[1]) for p in paired], [assess.encode(p[2]) for p in paired], workspace_mb, device_id)
     return report

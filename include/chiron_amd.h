@@ -571,6 +571,45 @@ chiron_status chiron_align_workspace_size(int64_t pairs, int64_t max_len, size_t
 chiron_status chiron_align_pairs(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const int64_t* ref_off, int64_t pairs,
                                  uint32_t flags, int32_t* edit_out, int32_t* match_out, int32_t* band_out, void* workspace, void* stream);
 
+/* Alignment traceback: the canonical optimal alignment of a pair whose (E, M) is known, one byte per column: 0 '=' (match),
+ * 1 'X' (mismatch), 2 'I' (a read base without a reference base), 3 'D' (a reference base without a read base).  Codes and the
+ * match rule are those of chiron_align_pairs.  Among the global alignments with the smallest E and then the largest M, the
+ * canonical one is the one whose column string, read from the LAST column to the first, is smallest under the order diagonal
+ * ('=' or 'X') < 'I' < 'D'.  Cell by cell: walking back from (n, m), each cell takes the first admissible predecessor in the
+ * order diagonal, up, left, where p is admissible for c when K(p) + cost(p -> c) = K(c) on the keys K = E * 2^32 - M.  Gaps in a
+ * repeat are therefore left-aligned.  It is a property of the inputs.  An infix alignment is traced as the read against the
+ * window's substring [s, e) that chiron_align_infix returned.
+ *
+ * The sweep runs once, at the half-width the known cost allows: a path that touches diagonal max(0, m-n) + x, x >= 1, costs at
+ * least 2x + |m-n|, so every alignment of cost E lies on the diagonals [min(0, m-n) - w, max(0, m-n) + w], w = (E - |m-n|) / 2
+ * (rounded down).  The back-pointers cover that band only: one row per anti-diagonal, 2 bits a cell, four cells a byte.
+ *
+ * The pair-size helper (host-only) gives one pair's back-pointer bytes and its band in diagonals from (n, m, edit), so a caller can
+ * plan batches against a memory budget.  CHIRON_ERR_INVALID: a negative length, edit < |m-n| or edit > max(n, m);
+ * CHIRON_ERR_OVERFLOW: a length past CHIRON_ALIGN_MAX_LEN.
+ *
+ * Workspace (device memory): the per-pair records and statuses, the packed codes and the columns (2 * max_len bytes a pair each),
+ * backpointer_bytes of back-pointers (the sum over the call's pairs) and -- when max_band, the call's widest band in diagonals,
+ * passes CHIRON_ALIGN_LDS_SLOTS -- one row of max_band + 1 64-bit cells for each of at most CHIRON_ALIGN_MAX_GROUPS workgroups.
+ * Larger values of any argument are fine.  Host-only.  CHIRON_ERR_INVALID: a negative argument.  CHIRON_ERR_OVERFLOW: max_len >
+ * CHIRON_ALIGN_MAX_LEN, pairs > 2^24 or backpointer_bytes > 2^46; within those bounds every offset the kernel forms is 64-bit.    */
+chiron_status chiron_align_trace_pair_size(int64_t n, int64_t m, int64_t edit, int64_t* backpointer_bytes, int64_t* band);
+chiron_status chiron_align_trace_workspace_size(int64_t pairs, int64_t backpointer_bytes, int64_t max_len, int64_t max_band, size_t* bytes);
+
+/* Trace `pairs` pairs in one launch.  codes, read_off, ref_off: as for chiron_align_pairs.  edit_in, match_in: HOST int32 [pairs],
+ * the pair's (E, M) as chiron_align_pairs or chiron_align_infix returned it.  ops_off: HOST int64 [pairs + 1], non-negative; pair
+ * p's columns are ops_out[ops_off[p] .. ops_off[p+1]), first column first, and ops_off[p+1] - ops_off[p] must be the pair's
+ * column count n + m - M - X = E + M.  status_out: HOST int32 [pairs]: 0 traced; 1 the kernel's own (E, M) of the pair is not
+ * the one passed in, and the pair's slice of ops_out is left untouched (the other pairs are unaffected).  workspace: device memory
+ * on device_id of chiron_align_trace_workspace_size bytes for the call's pairs.  flags: 0 (reserved).  Runs on `stream` (a
+ * hipStream_t; NULL = the null stream) and synchronises it before returning.  CHIRON_ERR_INVALID for a bad offset, a code above
+ * 4, edit < |m-n|, edit > max(n, m), a match count the lengths and edit rule out, or an ops_off that disagrees with the column
+ * count; CHIRON_ERR_OVERFLOW for a sequence longer than CHIRON_ALIGN_MAX_LEN; all before anything is copied or launched.
+ * pairs == 0 is a no-op.  Empty sequences are legal: all 'D' or all 'I'.                                                         */
+chiron_status chiron_align_trace(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const int64_t* ref_off, int64_t pairs,
+                                 const int32_t* edit_in, const int32_t* match_in, const int64_t* ops_off, uint32_t flags, uint8_t* ops_out,
+                                 int32_t* status_out, void* workspace, void* stream);
+
 /* Read mapping: infix (semi-global) alignment of a read against a genome window, unit costs, same codes as chiron_align_pairs.
  * Per pair (read a of n bases, window b of m bases), over every substring b[s:e), 0 <= s <= e <= m, and every global alignment
  * of a against it, the result is the tuple (E, M, s, e) that is smallest in this order: smallest edit cost E, then largest
