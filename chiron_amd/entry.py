@@ -235,6 +235,25 @@ def map_reads(args):
     return report
 
 
+def pileup(args):
+    """Consensus and variants from mapped reads: pileup.pileup_command (the columns of every alignment summed per genome position and
+    called on the GPU).  Writes <out>/consensus.fasta (a valid -r / -g for `assess` and `map`), <out>/variants.tsv and
+    <out>/pileup_report.json; exits non-zero on an input without a mapped.sam or without a usable alignment."""
+    from . import pileup as pileup_mod
+    try:
+        report = pileup_mod.pileup_command(args.input, args.genome, args.output, min_depth=args.min_depth, workspace_mb=args.workspace_mb,
+                                           device_id=args.device)
+    except ValueError as e:
+        sys.exit("pileup: %s" % e)
+    t = report["totals"]
+    print("pileup: %d alignments over %d positions, mean depth %.2f; %d substitutions, %d deletions, %d insertions applied; %d positions "
+          "below depth %d" % (report["alignments_used"], t["length"], t["mean_depth"], t["substitutions"], t["deletions"], t["insertions"],
+                              t["low_depth"], report["min_depth"]))
+    if report["alignments_used"] == 0:
+        sys.exit("pileup: %s holds no usable alignment" % report["sam"])
+    return report
+
+
 def label(args):
     """Labels from the model's own logits: label.label (CTC forced alignment of every read's frames to its reference bases on the
     GPU).  Writes <out>/<read>.signal + <out>/<read>.label, a folder `validate`, `finetune` and `train` take as -i, and
@@ -428,6 +447,16 @@ def build_parser():
                          "tag and mapped.sam is written.")
     mp.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     mp.set_defaults(func=map_reads)
+    pu = subparsers.add_parser("pileup", description="Consensus and variants from mapped reads: the alignment columns of mapped.sam summed "
+                               "per genome position and called on the GPU",
+                               help="Pile mapped reads up on the genome: consensus sequence, variants, report.")
+    pu.add_argument("-i", "--input", required=True, help="Output folder of `map --cigar` (its mapped.sam is read), or a SAM file.")
+    pu.add_argument("-g", "--genome", required=True, help="The genome FASTA the reads were mapped to.")
+    pu.add_argument("-o", "--output", required=True, help="Folder consensus.fasta, variants.tsv and pileup_report.json are written to.")
+    pu.add_argument("--min-depth", dest="min_depth", type=int, default=3, help="Positions covered by fewer alignments keep the genome's base.")
+    pu.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one genome tile, MiB.")
+    pu.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    pu.set_defaults(func=pileup)
     return parser
 
 

@@ -707,6 +707,65 @@ chiron_status chiron_ctc_align(int32_t device_id, const float* scores, const int
                                int32_t* start_out, double* score_out, int32_t* band_out, int32_t* status_out, void* workspace,
                                void* stream);
 
+/* Pileup: per genome position, what the mapped reads say there, and the consensus call.  An alignment is (pos, read, ops): pos a
+ * position in concatenated genome coordinates, read the read in genome orientation (codes 0..4), ops one byte per column as
+ * chiron_align_trace codes them (0 '=', 1 'X', 2 'I', 3 'D'); its '=', 'X' and 'I' columns together consume exactly the read, and m
+ * is the number of its '=', 'X' and 'D' columns, the reference bases it spans.  For column j let q be the reference-consuming
+ * columns before it and i the read-consuming ones.  With S = CHIRON_PILEUP_INS_SLOTS, per position g:
+ *   base[g][c], c = 0..4   alignments with a '=' or 'X' column at g = pos + q whose read base read[i] is c ('=' and 'X' are not told
+ *                          apart: the read base is counted, whatever the column says)
+ *   del[g]                 alignments with a 'D' column at g
+ *   ins[g][k][c], k < S    alignments whose (k+1)-th inserted base directly after the reference-consuming column at g is c; k is the
+ *                          number of 'I' columns between that column and this one
+ *   over[g]                alignments whose insertion after g is longer than S bases, each counted once (at its column k = S)
+ *   depth[g]               sum_c base[g][c] + del[g]
+ * An 'I' column with q = 0 (before the alignment's first reference base) or q = m (after its last) is clipping: it is counted
+ * nowhere per position and goes into the call's `clipped` total.
+ * The call at g, with r the reference code there, in integers only:
+ *   1. depth[g] < min_depth: r is emitted, status 1 (low depth), no insertion.
+ *   2. Otherwise the candidates A, C, G, T (count base[g][c]) and deletion (count del[g]) are compared by the key (count, c == r, -c)
+ *      for a base and (count, 0, -9) for the deletion; the largest key wins: ties go to the reference base, then to the smaller code,
+ *      and the deletion wins only when it strictly beats every base.  A winning count of 0 (only N was seen) emits r.  A winning
+ *      deletion emits nothing (code 5).
+ *   3. Insertion after g: slot k is emitted iff every slot below k was emitted and 2 * sum_c ins[g][k][c] > depth[g]; the base is
+ *      the largest of the slot's four base counts, ties to the smaller code, and N when all four are 0.
+ * over is reported and never acted on.  The counts are integer sums, so the result is a property of the inputs.
+ *
+ * Workspace (device memory): the per-alignment records (32 bytes each), read_bytes of codes, column_bytes of columns, the tile's
+ * reference codes, CHIRON_PILEUP_PLANES int32 count planes, the depths and the 8-byte call records of tile_len positions, each part
+ * rounded up to 256 bytes.  Larger values of any argument are fine.  Host-only.  CHIRON_ERR_INVALID: a negative argument.
+ * CHIRON_ERR_OVERFLOW: alignments > 2^24 (which keeps every int32 count below 2^31), tile_len > CHIRON_PILEUP_MAX_TILE, read_bytes
+ * or column_bytes > 2^24 * CHIRON_PILEUP_MAX_COLUMNS.                                                                             */
+#define CHIRON_PILEUP_INS_SLOTS 4
+#define CHIRON_PILEUP_PLANES (6 + 5 * CHIRON_PILEUP_INS_SLOTS + 1)
+#define CHIRON_PILEUP_MAX_COLUMNS (1 << 24)   /* columns, and read bases, of one alignment                                        */
+#define CHIRON_PILEUP_MAX_TILE (1 << 28)      /* positions of one call's tile                                                      */
+#define CHIRON_PILEUP_THREADS 256             /* one workgroup per alignment; its columns are taken 256 x 4 at a time               */
+chiron_status chiron_pileup_workspace_size(int64_t alignments, int64_t read_bytes, int64_t column_bytes, int64_t tile_len, size_t* bytes);
+
+/* Count and call one genome tile [g0, g1), 0 <= g0 <= g1.  Alignment p's read is codes[read_off[p] .. read_off[p+1]), its columns
+ * are ops[ops_off[p] .. ops_off[p+1]); read_off and ops_off are HOST int64 [alignments + 1], non-negative and non-decreasing; pos is
+ * HOST int64 [alignments]; ref_codes is HOST uint8 [g1 - g0], the genome's codes (0..4) of the tile.  Only positions inside the tile
+ * are counted; an alignment may lie partly or wholly outside it, and an insertion belongs to the tile of its anchor g.  Outputs,
+ * all HOST memory: counts_out (may be NULL) int32 [CHIRON_PILEUP_PLANES][g1 - g0], PLANAR -- planes 0..4 base, 5 del, 6 + 5k + c ins,
+ * the last plane over; depth_out int32 [g1 - g0]; call_out uint8 [g1 - g0][8] -- byte 0 the consensus code (0..3, 4 = N, 5 =
+ * deleted), byte 1 the number of inserted bases emitted, bytes 2..5 their codes (unused ones 0), byte 6 the status (0 called, 1 low
+ * depth), byte 7 zero; clipped_out int64 [1], the clipped 'I' columns of ALL alignments of the call: it does not depend on the tile
+ * (a caller that tiles a genome takes it from a call that holds every alignment once, or sums it over disjoint sets).  workspace:
+ * device memory on device_id of chiron_pileup_workspace_size(alignments, read bytes, column bytes, g1 - g0) bytes.  flags: 0
+ * (reserved).  Runs on `stream` (a hipStream_t; NULL = the null stream) -- a clear of the count planes, pileup_count_kernel (one
+ * workgroup of CHIRON_PILEUP_THREADS per alignment, alignment p on workgroup p mod the launch's group count, relaxed int32 atomic
+ * adds; every offset 64-bit) and pileup_call_kernel (one thread per position) -- and synchronises it before returning.
+ * CHIRON_ERR_INVALID for a bad offset, a code above 4 (read or reference), an op above 3, g0 < 0, g1 < g0, min_depth < 0, or an
+ * alignment whose '=', 'X' and 'I' columns do not add up to its read length; CHIRON_ERR_OVERFLOW for more than 2^24 alignments, an
+ * alignment past CHIRON_PILEUP_MAX_COLUMNS or a tile past CHIRON_PILEUP_MAX_TILE; all before anything is copied or launched.
+ * alignments == 0 still calls the tile (all low depth, or all reference when min_depth is 0).  g1 == g0 touches no device and
+ * writes clipped_out only.                                                                                                     */
+chiron_status chiron_pileup(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const uint8_t* ops, const int64_t* ops_off,
+                            const int64_t* pos, int64_t alignments, int64_t g0, int64_t g1, const uint8_t* ref_codes, int32_t min_depth,
+                            uint32_t flags, int32_t* counts_out, int32_t* depth_out, uint8_t* call_out, int64_t* clipped_out,
+                            void* workspace, void* stream);
+
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
 /* What kind of build this library is.  CHIRON_BUILD_TIMING: at least one object was compiled as a timing-only kernel variant
