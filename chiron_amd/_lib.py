@@ -8,6 +8,8 @@ import ctypes as C
 import os
 import sys
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CHIRON_AMD_LIB: another build of the same library (A/B measurements of kernel variants on one box)
 LIB_PATH = os.environ.get("CHIRON_AMD_LIB") or os.path.join(_HERE, "csrc", "libchiron_amd.so")
@@ -221,3 +223,36 @@ def load():
 def check(status):
     if status != OK:
         raise ChironError(status, load().chiron_last_error().decode("utf-8", "replace"))
+
+
+def sized(fn_name, *args):
+    """The byte count one of the library's host-only *_workspace_size functions writes through its last argument."""
+    n = C.c_size_t()
+    check(getattr(load(), fn_name)(*args, C.byref(n)))
+    return int(n.value)
+
+
+def pack_pairs(a, b):
+    """uint8 code arrays a[p] and b[p] as chiron_align_pairs, _infix and _trace take them: every a, then every b, then one pad
+    byte (the array is never empty).  -> (codes, lens_a, lens_b, off_a, off_b), the offsets into codes."""
+    codes = np.ascontiguousarray(np.concatenate(list(a) + list(b) + [np.zeros(1, np.uint8)]))
+    lens_a = np.array([len(s) for s in a], dtype=np.int64)
+    lens_b = np.array([len(s) for s in b], dtype=np.int64)
+    off_a = np.concatenate([[0], np.cumsum(lens_a)]).astype(np.int64)
+    off_b = (off_a[-1] + np.concatenate([[0], np.cumsum(lens_b)])).astype(np.int64)
+    return codes, lens_a, lens_b, off_a, off_b
+
+
+def device_workspace(nbytes, device_id, who, what):
+    """The workspace of one call on the GPU.  nbytes: the size, or a function that asks the library for it -- called here, after
+    torch is imported (its ROCm runtime has to come up before the library loads, see above) and before the GPU is touched, so
+    that a CHIRON_ERR_OVERFLOW comes first.  -> (lib, ws, stream pointer); the caller drops ws after the call."""
+    import torch
+    if callable(nbytes):
+        nbytes = nbytes()
+    lib = load()
+    if not torch.cuda.is_available():
+        raise RuntimeError("chiron_amd.%s needs a GPU: the %s has no CPU fallback" % (who, what))
+    dev = torch.device("cuda", device_id)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    return lib, ws, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

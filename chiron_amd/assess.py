@@ -164,9 +164,7 @@ def rates(match, mismatch, insertion, deletion):
 
 
 def workspace_size(pairs, max_len):
-    n = C.c_size_t()
-    _lib.check(_lib.load().chiron_align_workspace_size(pairs, max_len, C.byref(n)))
-    return int(n.value)
+    return _lib.sized("chiron_align_workspace_size", pairs, max_len)
 
 
 def align_pairs(reads, refs, device_id=0):
@@ -180,26 +178,14 @@ def align_pairs(reads, refs, device_id=0):
     out = np.zeros(pairs, dtype=RESULT_DTYPE)
     if pairs == 0:
         return out
-    codes = np.ascontiguousarray(np.concatenate(a + b + [np.zeros(1, np.uint8)]))
-    lens_a = np.array([len(s) for s in a], dtype=np.int64)
-    lens_b = np.array([len(s) for s in b], dtype=np.int64)
-    read_off = np.concatenate([[0], np.cumsum(lens_a)]).astype(np.int64)
-    ref_off = (read_off[-1] + np.concatenate([[0], np.cumsum(lens_b)])).astype(np.int64)
+    codes, lens_a, lens_b, read_off, ref_off = _lib.pack_pairs(a, b)
     max_len = int(max(lens_a.max(), lens_b.max()))
-    import torch                                  # before the library loads: its ROCm runtime has to come up first (_lib.py)
-    nbytes = workspace_size(pairs, max_len)       # raises CHIRON_ERR_OVERFLOW past MAX_LEN before the GPU is touched
-    lib = _lib.load()
-    if not torch.cuda.is_available():
-        raise RuntimeError("chiron_amd.assess.align_pairs needs a GPU: the alignment has no CPU fallback")
-    dev = torch.device("cuda", device_id)
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    lib, ws, stream = _lib.device_workspace(lambda: workspace_size(pairs, max_len), device_id, "assess.align_pairs", "alignment")
     edit = np.zeros(pairs, dtype=np.int32)
     match = np.zeros(pairs, dtype=np.int32)
     band = np.zeros(pairs, dtype=np.int32)
-    stream = torch.cuda.current_stream(dev)
     _lib.check(lib.chiron_align_pairs(device_id, codes.ctypes.data, read_off.ctypes.data, ref_off.ctypes.data, pairs, 0,
-                                      edit.ctypes.data, match.ctypes.data, band.ctypes.data, ws.data_ptr(),
-                                      C.c_void_p(stream.cuda_stream)))
+                                      edit.ctypes.data, match.ctypes.data, band.ctypes.data, ws.data_ptr(), stream))
     del ws
     out["read_len"], out["ref_len"], out["edit"], out["match"], out["band"] = lens_a, lens_b, edit, match, band
     x, i, d = counts(lens_a, lens_b, edit.astype(np.int64), match.astype(np.int64))
@@ -221,9 +207,7 @@ def trace_pair_size(n, m, edit):
 
 
 def trace_workspace_size(pairs, backpointer_bytes, max_len, max_band):
-    n = C.c_size_t()
-    _lib.check(_lib.load().chiron_align_trace_workspace_size(pairs, backpointer_bytes, max_len, max_band, C.byref(n)))
-    return int(n.value)
+    return _lib.sized("chiron_align_trace_workspace_size", pairs, backpointer_bytes, max_len, max_band)
 
 
 def plan_trace_batches(read_lens, ref_lens, edits, budget_bytes):
@@ -248,26 +232,15 @@ def plan_trace_batches(read_lens, ref_lens, edits, budget_bytes):
 def trace_pairs(a, b, edit, match, workspace_bytes, device_id=0):
     """One chiron_align_trace call on code arrays a[p], b[p] with their known (edit, match).  -> ([uint8 op arrays], status)."""
     pairs = len(a)
-    codes = np.ascontiguousarray(np.concatenate(list(a) + list(b) + [np.zeros(1, np.uint8)]))
-    lens_a = np.array([len(s) for s in a], dtype=np.int64)
-    lens_b = np.array([len(s) for s in b], dtype=np.int64)
-    read_off = np.concatenate([[0], np.cumsum(lens_a)]).astype(np.int64)
-    ref_off = (read_off[-1] + np.concatenate([[0], np.cumsum(lens_b)])).astype(np.int64)
+    codes, _, _, read_off, ref_off = _lib.pack_pairs(a, b)
     edit = np.ascontiguousarray(edit, dtype=np.int32)
     match = np.ascontiguousarray(match, dtype=np.int32)
     ops_off = np.concatenate([[0], np.cumsum(edit.astype(np.int64) + match)]).astype(np.int64)
     ops = np.zeros(max(int(ops_off[-1]), 1), dtype=np.uint8)
     status = np.zeros(pairs, dtype=np.int32)
-    import torch
-    lib = _lib.load()
-    if not torch.cuda.is_available():
-        raise RuntimeError("chiron_amd.assess.align_ops needs a GPU: the traceback has no CPU fallback")
-    dev = torch.device("cuda", device_id)
-    ws = torch.empty(max(workspace_bytes, 256), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev)
+    lib, ws, stream = _lib.device_workspace(workspace_bytes, device_id, "assess.align_ops", "traceback")
     _lib.check(lib.chiron_align_trace(device_id, codes.ctypes.data, read_off.ctypes.data, ref_off.ctypes.data, pairs, edit.ctypes.data,
-                                      match.ctypes.data, ops_off.ctypes.data, 0, ops.ctypes.data, status.ctypes.data, ws.data_ptr(),
-                                      C.c_void_p(stream.cuda_stream)))
+                                      match.ctypes.data, ops_off.ctypes.data, 0, ops.ctypes.data, status.ctypes.data, ws.data_ptr(), stream))
     del ws
     return [ops[ops_off[p]:ops_off[p + 1]].copy() for p in range(pairs)], status
 

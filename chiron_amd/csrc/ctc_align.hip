@@ -20,11 +20,10 @@
 #include <vector>
 
 #include "../../include/chiron_amd.h"
+#include "align_common.h"
 #include "kernels.h"
 
 namespace chiron {
-
-chiron_status set_error(chiron_status st, const char* fmt, ...);   // engine.hip
 
 namespace {
 
@@ -354,10 +353,9 @@ chiron_status label_layout(int64_t reads, const int64_t* frame_off, const int64_
   if (band0 < 0 || max_band < 0) return set_error(CHIRON_ERR_INVALID, "ctc_align: band0 %d / max_band %d is negative", band0, max_band);
   if (max_band > 0 && max_band < band0) return set_error(CHIRON_ERR_INVALID, "ctc_align: max_band %d below band0 %d", max_band, band0);
   if (reads == 0) return CHIRON_OK;
-  if (reads > ((int64_t)1 << 24)) return set_error(CHIRON_ERR_OVERFLOW, "ctc_align: %lld reads in one call, at most 2^24", (long long)reads);
+  if (reads > MAX_BATCH_ITEMS) return set_error(CHIRON_ERR_OVERFLOW, "ctc_align: %lld reads in one call, at most 2^24", (long long)reads);
   if (!frame_off || !label_off) return set_error(CHIRON_ERR_INVALID, "ctc_align: null offsets");
   if (frame_off[0] < 0 || label_off[0] < 0) return set_error(CHIRON_ERR_INVALID, "ctc_align: a negative first offset");
-  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const int64_t limit = (int64_t)1 << 46;   // bytes of back-pointers in one call: keeps every sum below far from 2^63
   int64_t bp = 0, widest_lds = 1, row_slots = 0;
   if (recs) recs->resize((size_t)reads);
@@ -396,15 +394,15 @@ chiron_status label_layout(int64_t reads, const int64_t* frame_off, const int64_
   l->frames = frames;
   l->bases = bases;
   l->read = 0;
-  l->scores = l->read + up((size_t)reads * sizeof(LabelRead));
-  l->labels = l->scores + up((size_t)frames * 5 * sizeof(float));
-  l->start = l->labels + up((size_t)bases);
-  l->score = l->start + up((size_t)bases * sizeof(int32_t));
-  l->band = l->score + up((size_t)reads * sizeof(double));
-  l->status = l->band + up((size_t)reads * sizeof(int32_t));
-  l->rows = l->status + up((size_t)reads * sizeof(int32_t));
-  l->bp = l->rows + up((size_t)l->groups * 2 * (size_t)l->row_slots * sizeof(double));
-  l->bytes = l->bp + up((size_t)bp);
+  l->scores = l->read + up256((size_t)reads * sizeof(LabelRead));
+  l->labels = l->scores + up256((size_t)frames * 5 * sizeof(float));
+  l->start = l->labels + up256((size_t)bases);
+  l->score = l->start + up256((size_t)bases * sizeof(int32_t));
+  l->band = l->score + up256((size_t)reads * sizeof(double));
+  l->status = l->band + up256((size_t)reads * sizeof(int32_t));
+  l->rows = l->status + up256((size_t)reads * sizeof(int32_t));
+  l->bp = l->rows + up256((size_t)l->groups * 2 * (size_t)l->row_slots * sizeof(double));
+  l->bytes = l->bp + up256((size_t)bp);
   return CHIRON_OK;
 }
 
@@ -453,18 +451,7 @@ extern "C" chiron_status chiron_ctc_align(int32_t device_id, const float* scores
   const uint8_t* lab = labels + label_off[0];
   for (int64_t i = 0; i < l.bases; ++i)
     if (lab[i] > 3) return set_error(CHIRON_ERR_INVALID, "chiron_ctc_align: code %d at base %lld outside 0..3", (int)lab[i], (long long)(label_off[0] + i));
-  if (!workspace) return set_error(CHIRON_ERR_INVALID, "chiron_ctc_align: null workspace");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_DEVICE, "no HIP device %d: libchiron_amd has no CPU fallback", device_id);
-  }
-  if (hipSetDevice(device_id) != hipSuccess) return set_error(CHIRON_ERR_DEVICE, "hipSetDevice(%d) failed", device_id);
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, workspace) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_INVALID, "chiron_ctc_align: workspace must be device memory on device %d", device_id);
-  }
+  if ((st = use_device_workspace("chiron_ctc_align", device_id, workspace))) return st;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)workspace;
   if (hipMemcpyAsync(ws + l.read, recs.data(), recs.size() * sizeof(LabelRead), hipMemcpyHostToDevice, stream) != hipSuccess ||

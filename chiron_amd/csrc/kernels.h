@@ -320,11 +320,12 @@ chiron_status ctc_check_rows(const int32_t* seq_len, const int32_t* labels, cons
 chiron_status ctc_sizes(int64_t batch, int64_t T, int64_t Lmax, uint32_t flags, int* S_ws, size_t* bytes);
 
 // ---------------------------------------------------------------------------------------------
-// Read-level assessment (assess.hip): banded global alignment with an exactness certificate, one workgroup per pair
+// Read-level assessment (assess.hip) and read mapping (map.hip): banded global / infix alignment with an exactness certificate,
+// one workgroup per pair, one sweep (align_common.h)
 // ---------------------------------------------------------------------------------------------
 struct AlignPair {
-  int64_t start;             // the read's first code in `codes`; the reference follows it directly
-  int32_t n, m;              // read and reference length
+  int64_t start;             // the read's first code in `codes`; the reference (the window) follows it directly
+  int32_t n, m;              // read and reference (window) length
 };
 struct AlignParams {
   const uint8_t* codes;      // packed: read 0, reference 0, read 1, ... (0..3 bases, 4 matches nothing)
@@ -332,7 +333,9 @@ struct AlignParams {
   int64_t pairs;
   int64_t* rows;             // [groups][row_slots] cells of bands wider than CHIRON_ALIGN_LDS_SLOTS, or null when none can be
   int64_t row_slots;
-  int32_t* out;              // [pairs][3] E, M, accepted band half-width
+  int32_t* out;              // align_kernel: [pairs][3] E, M, accepted band half-width; infix_kernel: [pairs][5] E, M, s, e, half-width
+  int32_t band0;             // infix_kernel: the first half-width; 0: the full table at once.  align_kernel does not read it: it
+                             // starts at the compile-time CHIRON_ALIGN_BAND0
 };
 // byte offsets of the workspace's parts and its size; CHIRON_ERR_OVERFLOW past what the kernel addresses
 struct AlignLayout {
@@ -341,27 +344,12 @@ struct AlignLayout {
   int groups;
 };
 chiron_status align_layout(int64_t pairs, int64_t max_len, AlignLayout* l);
+chiron_status infix_layout(int64_t pairs, int64_t max_read, int64_t max_window, AlignLayout* l);
+// the layout both are built on (assess.hip): code bytes and output words per pair, diagonals of the call's largest full table
+void pair_layout(int64_t pairs, int64_t code_bytes, int out_words, int64_t table, AlignLayout* l);
+AlignParams align_params(void* workspace, const AlignLayout& l, int64_t pairs, int32_t band0);
 int launch_align(const AlignParams& p, int groups, hipStream_t stream);  // 0 on success
-
-// ---------------------------------------------------------------------------------------------
-// Read mapping (map.hip): banded infix alignment of a read against a genome window, one workgroup per pair
-// ---------------------------------------------------------------------------------------------
-struct InfixParams {
-  const uint8_t* codes;      // packed: read 0, window 0, read 1, ... (an AlignPair each: the window follows its read directly)
-  const AlignPair* pair;     // [pairs]
-  int64_t pairs;
-  int64_t* rows;             // [groups][row_slots] cells of bands wider than CHIRON_INFIX_LDS_SLOTS, or null when none can be
-  int64_t row_slots;
-  int32_t* out;              // [pairs][5] E, M, s, e, accepted band half-width
-  int32_t band0;             // the first half-width; 0: the full table at once
-};
-struct InfixLayout {
-  size_t pair, out, codes, rows, bytes;
-  int64_t row_slots;
-  int groups;
-};
-chiron_status infix_layout(int64_t pairs, int64_t max_read, int64_t max_window, InfixLayout* l);
-int launch_infix(const InfixParams& p, int groups, hipStream_t stream);  // 0 on success
+int launch_infix(const AlignParams& p, int groups, hipStream_t stream);  // 0 on success
 
 // ---------------------------------------------------------------------------------------------
 // CTC forced alignment (ctc_align.hip): banded max-plus recursion with traceback, one workgroup per read

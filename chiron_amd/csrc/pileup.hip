@@ -27,10 +27,9 @@
 #include <vector>
 
 #include "../../include/chiron_amd.h"
+#include "align_common.h"
 
 namespace chiron {
-
-chiron_status set_error(chiron_status st, const char* fmt, ...);   // engine.hip
 
 namespace {
 
@@ -40,7 +39,6 @@ constexpr int S = CHIRON_PILEUP_INS_SLOTS;
 constexpr int PLANES = CHIRON_PILEUP_PLANES;
 constexpr int PLANE_DEL = 5, PLANE_INS = 6, PLANE_OVER = PLANES - 1;
 constexpr int MAX_GROUPS = 2048;              // workgroups of one launch
-constexpr int64_t MAX_ALIGNMENTS = (int64_t)1 << 24;
 static_assert(NT == 256, "the cross-wave step below is written for four waves of 64");
 
 struct PileupAln {
@@ -199,21 +197,20 @@ __global__ __launch_bounds__(CHIRON_PILEUP_THREADS) void pileup_call_kernel(cons
 chiron_status pileup_layout(int64_t alignments, int64_t read_bytes, int64_t column_bytes, int64_t tile, PileupLayout* l) {
   if (alignments < 0 || read_bytes < 0 || column_bytes < 0 || tile < 0)
     return set_error(CHIRON_ERR_INVALID, "pileup: negative alignments / read_bytes / column_bytes / tile_len");
-  if (alignments > MAX_ALIGNMENTS) return set_error(CHIRON_ERR_OVERFLOW, "pileup: %lld alignments in one call, at most 2^24", (long long)alignments);
+  if (alignments > MAX_BATCH_ITEMS) return set_error(CHIRON_ERR_OVERFLOW, "pileup: %lld alignments in one call, at most 2^24", (long long)alignments);
   if (tile > CHIRON_PILEUP_MAX_TILE)
     return set_error(CHIRON_ERR_OVERFLOW, "pileup: a tile of %lld positions, at most %d", (long long)tile, CHIRON_PILEUP_MAX_TILE);
   // an alignment has at most CHIRON_PILEUP_MAX_COLUMNS columns and as many read bases
-  if (read_bytes > MAX_ALIGNMENTS * CHIRON_PILEUP_MAX_COLUMNS || column_bytes > MAX_ALIGNMENTS * CHIRON_PILEUP_MAX_COLUMNS)
+  if (read_bytes > MAX_BATCH_ITEMS * CHIRON_PILEUP_MAX_COLUMNS || column_bytes > MAX_BATCH_ITEMS * CHIRON_PILEUP_MAX_COLUMNS)
     return set_error(CHIRON_ERR_OVERFLOW, "pileup: %lld read bytes / %lld column bytes, at most 2^48 each", (long long)read_bytes, (long long)column_bytes);
-  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   l->aln = 0;
-  l->codes = l->aln + up((size_t)alignments * sizeof(PileupAln));
-  l->ops = l->codes + up((size_t)read_bytes);
-  l->ref = l->ops + up((size_t)column_bytes);
-  l->counts = l->ref + up((size_t)tile);
-  l->depth = l->counts + up((size_t)PLANES * (size_t)tile * sizeof(int32_t));
-  l->call = l->depth + up((size_t)tile * sizeof(int32_t));
-  l->bytes = l->call + up((size_t)tile * 8);
+  l->codes = l->aln + up256((size_t)alignments * sizeof(PileupAln));
+  l->ops = l->codes + up256((size_t)read_bytes);
+  l->ref = l->ops + up256((size_t)column_bytes);
+  l->counts = l->ref + up256((size_t)tile);
+  l->depth = l->counts + up256((size_t)PLANES * (size_t)tile * sizeof(int32_t));
+  l->call = l->depth + up256((size_t)tile * sizeof(int32_t));
+  l->bytes = l->call + up256((size_t)tile * 8);
   return CHIRON_OK;
 }
 
@@ -239,7 +236,7 @@ extern "C" chiron_status chiron_pileup(int32_t device_id, const uint8_t* codes, 
   if (flags) return set_error(CHIRON_ERR_INVALID, "chiron_pileup: unknown flags 0x%x", flags);
   if (g0 < 0 || g1 < g0) return set_error(CHIRON_ERR_INVALID, "chiron_pileup: tile [%lld, %lld)", (long long)g0, (long long)g1);
   if (min_depth < 0) return set_error(CHIRON_ERR_INVALID, "chiron_pileup: min_depth %d", min_depth);
-  if (alignments > MAX_ALIGNMENTS) return set_error(CHIRON_ERR_OVERFLOW, "chiron_pileup: %lld alignments in one call, at most 2^24", (long long)alignments);
+  if (alignments > MAX_BATCH_ITEMS) return set_error(CHIRON_ERR_OVERFLOW, "chiron_pileup: %lld alignments in one call, at most 2^24", (long long)alignments);
   const int64_t tile = g1 - g0;
   if (tile > CHIRON_PILEUP_MAX_TILE)
     return set_error(CHIRON_ERR_OVERFLOW, "chiron_pileup: a tile of %lld positions, at most %d", (long long)tile, CHIRON_PILEUP_MAX_TILE);
@@ -247,18 +244,11 @@ extern "C" chiron_status chiron_pileup(int32_t device_id, const uint8_t* codes, 
   if (alignments > 0 && (!read_off || !ops_off || !pos)) return set_error(CHIRON_ERR_INVALID, "chiron_pileup: null operand");
   if (tile > 0 && (!ref_codes || !depth_out || !call_out)) return set_error(CHIRON_ERR_INVALID, "chiron_pileup: null ref_codes / depth_out / call_out");
   // offsets first (they bound what may be read of `codes` and `ops`), then every column and every code
-  for (int which = 0; which < 2 && alignments > 0; ++which) {
-    const int64_t* off = which ? ops_off : read_off;
-    const char* name = which ? "ops" : "read";
-    if (off[0] < 0) return set_error(CHIRON_ERR_INVALID, "chiron_pileup: %s_off[0] = %lld is negative", name, (long long)off[0]);
-    for (int64_t a = 0; a < alignments; ++a) {
-      if (off[a + 1] < off[a])
-        return set_error(CHIRON_ERR_INVALID, "chiron_pileup: %s_off[%lld] = %lld below its predecessor %lld", name, (long long)(a + 1),
-                         (long long)off[a + 1], (long long)off[a]);
-      if (off[a + 1] - off[a] > CHIRON_PILEUP_MAX_COLUMNS)
-        return set_error(CHIRON_ERR_OVERFLOW, "chiron_pileup: alignment %lld has %lld %s, at most %d", (long long)a, (long long)(off[a + 1] - off[a]),
-                         which ? "columns" : "read bases", CHIRON_PILEUP_MAX_COLUMNS);
-    }
+  if (alignments > 0) {
+    int64_t longest = 0, sum = 0;   // not needed here: the sizes below come from the offsets' ends
+    chiron_status st = check_offsets("chiron_pileup", "read", "alignment", "read bases", read_off, alignments, CHIRON_PILEUP_MAX_COLUMNS, &longest, &sum);
+    if (!st) st = check_offsets("chiron_pileup", "ops", "alignment", "columns", ops_off, alignments, CHIRON_PILEUP_MAX_COLUMNS, &longest, &sum);
+    if (st) return st;
   }
   const int64_t read_lo = alignments ? read_off[0] : 0, ops_lo = alignments ? ops_off[0] : 0;
   const int64_t read_bytes = alignments ? read_off[alignments] - read_lo : 0, column_bytes = alignments ? ops_off[alignments] - ops_lo : 0;
@@ -301,18 +291,7 @@ extern "C" chiron_status chiron_pileup(int32_t device_id, const uint8_t* codes, 
   PileupLayout l;
   chiron_status st = pileup_layout(alignments, read_bytes, column_bytes, tile, &l);
   if (st) return st;
-  if (!workspace) return set_error(CHIRON_ERR_INVALID, "chiron_pileup: null workspace");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_DEVICE, "no HIP device %d: libchiron_amd has no CPU fallback", device_id);
-  }
-  if (hipSetDevice(device_id) != hipSuccess) return set_error(CHIRON_ERR_DEVICE, "hipSetDevice(%d) failed", device_id);
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, workspace) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_INVALID, "chiron_pileup: workspace must be device memory on device %d", device_id);
-  }
+  if ((st = use_device_workspace("chiron_pileup", device_id, workspace))) return st;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)workspace;
   const size_t count_bytes = (size_t)PLANES * (size_t)tile * sizeof(int32_t);

@@ -5,7 +5,8 @@
 // (n, m), every cell takes its first admissible predecessor in the order diagonal, up, left.  That order is fixed, so one 2-bit
 // pointer per cell, written during the forward sweep, is the whole record.              (include/chiron_amd.h)
 //
-// Work mapping: one workgroup per pair, assess.hip's anti-diagonal sweep over one array of keys E * 2^32 - M indexed by diagonal,
+// Work mapping: one workgroup per pair, assess.hip's recurrence over one array of keys E * 2^32 - M indexed by diagonal (the band
+// clip, the anti-diagonal's range, the row choice and the key are align_common.h's; the sweep is this file's own, below),
 // run ONCE at the half-width the known cost allows: a path that touches diagonal max(0, m-n) + x costs at least 2x + |m-n|, so
 // every alignment of cost E lies inside w* = (E - |m-n|) / 2 and no doubling is needed.  The cells of one anti-diagonal share
 // its parity, so the array is kept as two halves, even slots and odd slots: cell c of anti-diagonal k (slot 2c + parity) is entry
@@ -20,21 +21,17 @@
 #include <vector>
 
 #include "../../include/chiron_amd.h"
+#include "align_common.h"
 #include "kernels.h"
 
 namespace chiron {
 
-chiron_status set_error(chiron_status st, const char* fmt, ...);   // engine.hip
-
 namespace {
 
-constexpr int64_t ALIGN_GAP = (int64_t)1 << 32;
+constexpr int64_t ALIGN_GAP = KEY32_EDIT;
 constexpr int NT = CHIRON_ALIGN_THREADS;
 constexpr int STATUS_MISMATCH = 1;           // the end cell's (E, M) is not what the caller passed in
 constexpr int STATUS_INTERNAL = 2;           // a guard of the kernel fired: reported as CHIRON_ERR_STATE, never returned to the caller
-
-__device__ inline int imax(int a, int b) { return a > b ? a : b; }
-__device__ inline int imin(int a, int b) { return a < b ? a : b; }
 
 // the sweep over the band [dlo, dhi] (clipped to the table's diagonals -n .. m); writes every cell's pointer, returns the key of (n, m)
 __device__ __forceinline__ int64_t traced_pass(int64_t* row, uint8_t* __restrict__ bp, const uint8_t* __restrict__ a,
@@ -42,10 +39,8 @@ __device__ __forceinline__ int64_t traced_pass(int64_t* row, uint8_t* __restrict
   const int tid = threadIdx.x;
   const int half = (dhi - dlo + 2) >> 1;      // entries of the even half; the odd half follows it
   for (int k = 0; k <= n + m; ++k) {
-    // the anti-diagonal's cells inside the table and the band: 0 <= i = (k-d)/2 <= n, 0 <= j = (k+d)/2 <= m
-    const int lo = imax(imax(dlo, -k), k - 2 * n);
-    const int hi = imin(imin(dhi, k), 2 * m - k);
-    const int first = lo + ((lo + k) & 1);
+    const DiagRange r = diag_range(k, n, m, dlo, dhi);
+    const int first = r.first, hi = r.hi;
     if (first <= hi) {
       const int par = (k - dlo) & 1;          // the parity of this anti-diagonal's slots d - dlo
       int64_t* own = row + par * half;        // step k rewrites its own half in place (each entry's old value, from k-2, is read by its own thread only)
@@ -98,8 +93,8 @@ __device__ __forceinline__ int64_t traced_pass(int64_t* row, uint8_t* __restrict
 // One lane: rederive (E, M) from the end cell's key, then walk the pointers from (n, m) and fill the columns from the last one down.
 __device__ int walk(const TracePair& pr, int64_t key, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
                     const uint8_t* bp, uint8_t* __restrict__ ops) {
-  const int E = (int)((key + (ALIGN_GAP >> 1)) >> 32);
-  const int M = (int)((int64_t)E * ALIGN_GAP - key);
+  int E, M;
+  key32_decode(key, &E, &M);
   if (E != pr.E || M != pr.M) return STATUS_MISMATCH;
   const int dlo = pr.dlo, slots = pr.dhi - pr.dlo + 1;
   int i = pr.n, j = pr.m, pos = E + M;
@@ -136,15 +131,10 @@ __global__ __launch_bounds__(CHIRON_ALIGN_THREADS) void trace_kernel(TraceParams
     const uint8_t* a = p.codes + pr.start;
     const uint8_t* b = a + n;
     uint8_t* bp = p.bp + pr.bp;
-    const int slots = dhi - dlo + 1;
-    // the host sized the row for the call's widest band; a pair that would not fit cannot occur, and is answered with a status
-    // rather than with a write past the row.  The two halves take slots + 1 entries when slots is odd (LDS_SLOTS is even).
+    // the two halves take slots + 1 entries when slots is odd (LDS_SLOTS is even): a workspace row has to be longer than slots
     int64_t key;
-    if (slots <= CHIRON_ALIGN_LDS_SLOTS) {
-      key = traced_pass(lds_row, bp, a, b, n, m, dlo, dhi, pr.rowbytes);
-    } else if (ws_row && slots < p.row_slots) {
-      key = traced_pass(ws_row, bp, a, b, n, m, dlo, dhi, pr.rowbytes);
-    } else {
+    if (!with_row(lds_row, ws_row, dhi - dlo + 1, p.row_slots - 1,
+                  [&](int64_t* row) { key = traced_pass(row, bp, a, b, n, m, dlo, dhi, pr.rowbytes); })) {
       if (threadIdx.x == 0) p.status[q] = STATUS_INTERNAL;
       continue;
     }
@@ -156,14 +146,11 @@ __global__ __launch_bounds__(CHIRON_ALIGN_THREADS) void trace_kernel(TraceParams
 
 TraceBand trace_band(int64_t n, int64_t m, int64_t E) {
   const int64_t gap = m > n ? m - n : n - m;
-  const int64_t w = (E - gap) / 2;
-  int64_t dlo = (m < n ? m - n : 0) - w, dhi = (m > n ? m - n : 0) + w;
-  if (dlo < -n) dlo = -n;
-  if (dhi > m) dhi = m;
+  const Diagonals bd = band_clip((int)n, (int)m, (int)((E - gap) / 2));   // check_pair has bounded n, m and E by CHIRON_ALIGN_MAX_LEN
   TraceBand t;
-  t.dlo = (int32_t)dlo;
-  t.dhi = (int32_t)dhi;
-  t.width = dhi - dlo + 1;
+  t.dlo = bd.dlo;
+  t.dhi = bd.dhi;
+  t.width = (int64_t)bd.dhi - bd.dlo + 1;
   const int64_t cells = (t.width + 1) >> 1;   // of one anti-diagonal
   t.rowbytes = (int32_t)((cells + 3) >> 2);
   t.bytes = (n + m + 1) * (int64_t)t.rowbytes;
@@ -187,21 +174,20 @@ chiron_status trace_layout(int64_t pairs, int64_t backpointer_bytes, int64_t max
     return set_error(CHIRON_ERR_INVALID, "align_trace: negative pairs / backpointer_bytes / max_len / max_band");
   if (max_len > CHIRON_ALIGN_MAX_LEN)
     return set_error(CHIRON_ERR_OVERFLOW, "align_trace: a sequence of %lld bases, the kernel takes at most %d", (long long)max_len, CHIRON_ALIGN_MAX_LEN);
-  if (pairs > ((int64_t)1 << 24)) return set_error(CHIRON_ERR_OVERFLOW, "align_trace: %lld pairs in one call, at most 2^24", (long long)pairs);
+  if (pairs > MAX_BATCH_ITEMS) return set_error(CHIRON_ERR_OVERFLOW, "align_trace: %lld pairs in one call, at most 2^24", (long long)pairs);
   if (backpointer_bytes > ((int64_t)1 << 46))
     return set_error(CHIRON_ERR_OVERFLOW, "align_trace: the back-pointers of the call pass 2^46 bytes: split the batch");
   if (max_band > 2 * max_len + 1) max_band = 2 * max_len + 1;   // no band is wider than the table
   // pairs <= 2^24 and max_len <= 2^17: every product below stays under 2^46
-  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   l->groups = (int)(pairs < CHIRON_ALIGN_MAX_GROUPS ? pairs : CHIRON_ALIGN_MAX_GROUPS);
   l->row_slots = max_band > CHIRON_ALIGN_LDS_SLOTS ? ((max_band + 2) & ~(int64_t)1) : 0;
   l->pair = 0;
-  l->status = l->pair + up((size_t)pairs * sizeof(TracePair));
-  l->codes = l->status + up((size_t)pairs * sizeof(int32_t));
-  l->ops = l->codes + up((size_t)pairs * 2 * (size_t)max_len);
-  l->rows = l->ops + up((size_t)pairs * 2 * (size_t)max_len);
-  l->bp = l->rows + up((size_t)l->groups * (size_t)l->row_slots * sizeof(int64_t));
-  l->bytes = l->bp + up((size_t)backpointer_bytes);
+  l->status = l->pair + up256((size_t)pairs * sizeof(TracePair));
+  l->codes = l->status + up256((size_t)pairs * sizeof(int32_t));
+  l->ops = l->codes + up256((size_t)pairs * 2 * (size_t)max_len);
+  l->rows = l->ops + up256((size_t)pairs * 2 * (size_t)max_len);
+  l->bp = l->rows + up256((size_t)l->groups * (size_t)l->row_slots * sizeof(int64_t));
+  l->bytes = l->bp + up256((size_t)backpointer_bytes);
   return CHIRON_OK;
 }
 
@@ -238,99 +224,57 @@ extern "C" chiron_status chiron_align_trace_workspace_size(int64_t pairs, int64_
 extern "C" chiron_status chiron_align_trace(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const int64_t* ref_off,
                                             int64_t pairs, const int32_t* edit_in, const int32_t* match_in, const int64_t* ops_off,
                                             uint32_t flags, uint8_t* ops_out, int32_t* status_out, void* workspace, void* stream_) {
-  if (pairs < 0) return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: pairs %lld", (long long)pairs);
-  if (flags) return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: unknown flags 0x%x", flags);
+  const char* const who = "chiron_align_trace";
+  if (pairs < 0) return set_error(CHIRON_ERR_INVALID, "%s: pairs %lld", who, (long long)pairs);
+  if (flags) return set_error(CHIRON_ERR_INVALID, "%s: unknown flags 0x%x", who, flags);
   if (pairs == 0) return CHIRON_OK;
-  if (pairs > ((int64_t)1 << 24)) return set_error(CHIRON_ERR_OVERFLOW, "chiron_align_trace: %lld pairs in one call, at most 2^24", (long long)pairs);
-  if (!read_off || !ref_off || !edit_in || !match_in || !ops_off || !status_out) return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: null operand");
+  if (pairs > MAX_BATCH_ITEMS) return set_error(CHIRON_ERR_OVERFLOW, "%s: %lld pairs in one call, at most 2^24", who, (long long)pairs);
+  if (!read_off || !ref_off || !edit_in || !match_in || !ops_off || !status_out) return set_error(CHIRON_ERR_INVALID, "%s: null operand", who);
   // offsets first (they bound what may be read of `codes`), then (E, M) against the lengths and the columns, then the codes
-  int64_t total = 0;
-  for (int which = 0; which < 2; ++which) {
-    const int64_t* off = which ? ref_off : read_off;
-    if (off[0] < 0) return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: %s_off[0] = %lld is negative", which ? "ref" : "read", (long long)off[0]);
-    for (int64_t q = 0; q < pairs; ++q) {
-      if (off[q + 1] < off[q])
-        return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: %s_off[%lld] = %lld below its predecessor %lld", which ? "ref" : "read",
-                         (long long)(q + 1), (long long)off[q + 1], (long long)off[q]);
-      const int64_t len = off[q + 1] - off[q];
-      if (len > CHIRON_ALIGN_MAX_LEN)
-        return set_error(CHIRON_ERR_OVERFLOW, "chiron_align_trace: %s %lld has %lld bases, at most %d", which ? "reference" : "read",
-                         (long long)q, (long long)len, CHIRON_ALIGN_MAX_LEN);
-      total += len;
-    }
-  }
-  if (ops_off[0] < 0) return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: ops_off[0] = %lld is negative", (long long)ops_off[0]);
+  int64_t max_len = 0, total = 0;
+  chiron_status st = check_offsets(who, "read", "read", "bases", read_off, pairs, CHIRON_ALIGN_MAX_LEN, &max_len, &total);
+  if (!st) st = check_offsets(who, "ref", "reference", "bases", ref_off, pairs, CHIRON_ALIGN_MAX_LEN, &max_len, &total);
+  if (st) return st;
+  if (ops_off[0] < 0) return set_error(CHIRON_ERR_INVALID, "%s: ops_off[0] = %lld is negative", who, (long long)ops_off[0]);
   std::vector<TracePair> recs((size_t)pairs);
-  int64_t at = 0, bp = 0, max_len = 0, max_band = 0;
+  int64_t bp = 0, max_band = 0;
   for (int64_t q = 0; q < pairs; ++q) {
     const int64_t n = read_off[q + 1] - read_off[q], m = ref_off[q + 1] - ref_off[q], E = edit_in[q], M = match_in[q];
-    chiron_status st = check_pair("chiron_align_trace", q, n, m, E);
-    if (st) return st;
+    if ((st = check_pair(who, q, n, m, E))) return st;
     // X = n + m - 2M - E mismatches, and the alignment has n + m - M - X = E + M columns
     if (M < 0 || n + m - 2 * M - E < 0)
-      return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: pair %lld (%lld against %lld bases, edit %lld) cannot have %lld matches", (long long)q,
+      return set_error(CHIRON_ERR_INVALID, "%s: pair %lld (%lld against %lld bases, edit %lld) cannot have %lld matches", who, (long long)q,
                        (long long)n, (long long)m, (long long)E, (long long)M);
     if (ops_off[q + 1] - ops_off[q] != E + M)
-      return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: ops_off gives pair %lld %lld columns, its alignment has %lld", (long long)q,
+      return set_error(CHIRON_ERR_INVALID, "%s: ops_off gives pair %lld %lld columns, its alignment has %lld", who, (long long)q,
                        (long long)(ops_off[q + 1] - ops_off[q]), (long long)(E + M));
     const TraceBand t = trace_band(n, m, E);
-    TracePair& r = recs[(size_t)q];
-    r.start = at;
+    TracePair& r = recs[(size_t)q];   // start, n and m: pack_codes below
     r.bp = bp;
     r.ops = ops_off[q] - ops_off[0];
-    r.n = (int32_t)n;
-    r.m = (int32_t)m;
     r.E = (int32_t)E;
     r.M = (int32_t)M;
     r.dlo = t.dlo;
     r.dhi = t.dhi;
     r.rowbytes = t.rowbytes;
     r.pad_ = 0;
-    at += n + m;
     bp += t.bytes;
-    if (bp > ((int64_t)1 << 46)) return set_error(CHIRON_ERR_OVERFLOW, "chiron_align_trace: the back-pointers of the call pass 2^46 bytes: split the batch");
-    if (n > max_len) max_len = n;
-    if (m > max_len) max_len = m;
+    if (bp > ((int64_t)1 << 46)) return set_error(CHIRON_ERR_OVERFLOW, "%s: the back-pointers of the call pass 2^46 bytes: split the batch", who);
     if (t.width > max_band) max_band = t.width;
   }
-  if (total > 0 && !codes) return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: null codes");
+  if (total > 0 && !codes) return set_error(CHIRON_ERR_INVALID, "%s: null codes", who);
   const int64_t columns = ops_off[pairs] - ops_off[0];
-  if (columns > 0 && !ops_out) return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: null ops_out");
+  if (columns > 0 && !ops_out) return set_error(CHIRON_ERR_INVALID, "%s: null ops_out", who);
   std::vector<uint8_t> packed((size_t)total);
-  for (int64_t q = 0; q < pairs; ++q) {
-    int64_t to = recs[(size_t)q].start;
-    for (int which = 0; which < 2; ++which) {
-      const int64_t lo = which ? ref_off[q] : read_off[q], len = which ? recs[(size_t)q].m : recs[(size_t)q].n;
-      for (int64_t i = 0; i < len; ++i) {
-        const uint8_t c = codes[lo + i];
-        if (c > 4)
-          return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: code %d at %lld of %s %lld outside 0..4", (int)c, (long long)i,
-                           which ? "reference" : "read", (long long)q);
-        packed[(size_t)(to + i)] = c;
-      }
-      to += len;
-    }
-  }
   TraceLayout l;
-  chiron_status st = trace_layout(pairs, bp, max_len, max_band, &l);
-  if (st) return st;
-  if (!workspace) return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: null workspace");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_DEVICE, "no HIP device %d: libchiron_amd has no CPU fallback", device_id);
-  }
-  if (hipSetDevice(device_id) != hipSuccess) return set_error(CHIRON_ERR_DEVICE, "hipSetDevice(%d) failed", device_id);
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, workspace) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_INVALID, "chiron_align_trace: workspace must be device memory on device %d", device_id);
-  }
+  if ((st = pack_codes(who, "read", "reference", codes, read_off, ref_off, pairs, recs.data(), packed.data()))) return st;
+  if ((st = trace_layout(pairs, bp, max_len, max_band, &l))) return st;
+  if ((st = use_device_workspace(who, device_id, workspace))) return st;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)workspace;
   if (hipMemcpyAsync(ws + l.pair, recs.data(), recs.size() * sizeof(TracePair), hipMemcpyHostToDevice, stream) != hipSuccess ||
       (total > 0 && hipMemcpyAsync(ws + l.codes, packed.data(), packed.size(), hipMemcpyHostToDevice, stream) != hipSuccess))
-    return set_error(CHIRON_ERR_DEVICE, "chiron_align_trace: copying the pairs to the device failed");
+    return set_error(CHIRON_ERR_DEVICE, "%s: copying the pairs to the device failed", who);
   TraceParams p;
   p.codes = (const uint8_t*)(ws + l.codes);
   p.pair = (const TracePair*)(ws + l.pair);
@@ -340,14 +284,14 @@ extern "C" chiron_status chiron_align_trace(int32_t device_id, const uint8_t* co
   p.bp = (uint8_t*)(ws + l.bp);
   p.ops = (uint8_t*)(ws + l.ops);
   p.status = (int32_t*)(ws + l.status);
-  if (launch_trace(p, l.groups, stream) != 0) return set_error(CHIRON_ERR_DEVICE, "chiron_align_trace: launch failed");
+  if (launch_trace(p, l.groups, stream) != 0) return set_error(CHIRON_ERR_DEVICE, "%s: launch failed", who);
   std::vector<uint8_t> cols((size_t)columns);
   if (hipMemcpyAsync(status_out, ws + l.status, (size_t)pairs * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
       (columns > 0 && hipMemcpyAsync(cols.data(), ws + l.ops, cols.size(), hipMemcpyDeviceToHost, stream) != hipSuccess) ||
       hipStreamSynchronize(stream) != hipSuccess)
-    return set_error(CHIRON_ERR_DEVICE, "chiron_align_trace: the traceback kernel failed (%s)", hipGetErrorString(hipGetLastError()));
+    return set_error(CHIRON_ERR_DEVICE, "%s: the traceback kernel failed (%s)", who, hipGetErrorString(hipGetLastError()));
   for (int64_t q = 0; q < pairs; ++q)
-    if (status_out[q] == STATUS_INTERNAL) return set_error(CHIRON_ERR_STATE, "chiron_align_trace: pair %lld outgrew its workspace", (long long)q);
+    if (status_out[q] == STATUS_INTERNAL) return set_error(CHIRON_ERR_STATE, "%s: pair %lld outgrew its workspace", who, (long long)q);
   // a pair whose (E, M) the kernel did not confirm keeps whatever its slice of ops_out held
   for (int64_t q = 0; q < pairs; ++q) {
     const int64_t len = ops_off[q + 1] - ops_off[q];

@@ -8,7 +8,6 @@ from an outside resquiggler (chiron/utils/raw.py reads Tombo's tables); here not
 
 A banded alignment is the best path inside its band, not a certified optimum (include/chiron_amd.h); the report carries the band
 each read stopped at and its mean log-probability per frame, which is what to filter on.  There is no CPU fallback."""
-import ctypes as C
 import json
 import logging
 import os
@@ -37,9 +36,7 @@ def workspace_size(frames, bases, band0, max_band):
     if len(frames) != len(bases):
         raise ValueError("%d frame counts against %d base counts" % (len(frames), len(bases)))
     fo, lo = _offsets(frames), _offsets(bases)
-    n = C.c_size_t()
-    _lib.check(_lib.load().chiron_ctc_align_workspace_size(len(frames), fo.ctypes.data, lo.ctypes.data, band0, max_band, C.byref(n)))
-    return int(n.value)
+    return _lib.sized("chiron_ctc_align_workspace_size", len(frames), fo.ctypes.data, lo.ctypes.data, band0, max_band)
 
 
 def plan_batches(frames, bases, band0, max_band, budget_bytes):
@@ -76,18 +73,12 @@ def align(scores_list, labels_list, band0=BAND0, max_band=MAX_BAND, device_id=0)
     scores = np.ascontiguousarray(np.concatenate(xs + [np.zeros((1, 5), np.float32)]))
     labels = np.ascontiguousarray(np.concatenate(ls + [np.zeros(1, np.uint8)]))
     start = np.full(int(label_off[-1]) + 1, -1, dtype=np.int32)
-    import torch                                  # before the library loads: its ROCm runtime has to come up first (_lib.py)
-    lib = _lib.load()
-    n = C.c_size_t()
-    _lib.check(lib.chiron_ctc_align_workspace_size(reads, frame_off.ctypes.data, label_off.ctypes.data, band0, max_band, C.byref(n)))
-    if not torch.cuda.is_available():
-        raise RuntimeError("chiron_amd.label.align needs a GPU: the alignment has no CPU fallback")
-    dev = torch.device("cuda", device_id)
-    ws = torch.empty(max(int(n.value), 256), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev)
+    lib, ws, stream = _lib.device_workspace(lambda: _lib.sized("chiron_ctc_align_workspace_size", reads, frame_off.ctypes.data,
+                                                               label_off.ctypes.data, band0, max_band),
+                                            device_id, "label.align", "alignment")
     _lib.check(lib.chiron_ctc_align(device_id, scores.ctypes.data, frame_off.ctypes.data, labels.ctypes.data, label_off.ctypes.data,
                                     reads, band0, max_band, 0, start.ctypes.data, score.ctypes.data, band.ctypes.data,
-                                    status.ctypes.data, ws.data_ptr(), C.c_void_p(stream.cuda_stream)))
+                                    status.ctypes.data, ws.data_ptr(), stream))
     del ws
     return {"start": [start[label_off[r]:label_off[r + 1]].copy() for r in range(reads)], "score": score, "band": band, "status": status}
 

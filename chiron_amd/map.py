@@ -24,7 +24,6 @@ reference can only come from the kernel:
            outside: the read's slack doubles and it is aligned again in a follow-up launch, at most three times; then `edge`.
 There is no CPU fallback: without the library or a GPU, align_infix raises.
 """
-import ctypes as C
 import json
 import os
 
@@ -54,9 +53,7 @@ def decode(codes):
 # the kernel
 # ----------------------------------------------------------------------------------------------------------------------------
 def workspace_size(pairs, max_read, max_window):
-    n = C.c_size_t()
-    _lib.check(_lib.load().chiron_align_infix_workspace_size(pairs, max_read, max_window, C.byref(n)))
-    return int(n.value)
+    return _lib.sized("chiron_align_infix_workspace_size", pairs, max_read, max_window)
 
 
 def align_infix(reads, windows, band0=BAND0, device_id=0):
@@ -70,23 +67,13 @@ def align_infix(reads, windows, band0=BAND0, device_id=0):
         return out
     a = [assess.encode(s) for s in reads]
     b = [assess.encode(s) for s in windows]
-    codes = np.ascontiguousarray(np.concatenate(a + b + [np.zeros(1, np.uint8)]))
-    lens_a = np.array([len(s) for s in a], dtype=np.int64)
-    lens_b = np.array([len(s) for s in b], dtype=np.int64)
-    read_off = np.concatenate([[0], np.cumsum(lens_a)]).astype(np.int64)
-    win_off = (read_off[-1] + np.concatenate([[0], np.cumsum(lens_b)])).astype(np.int64)
-    import torch                                  # before the library loads: its ROCm runtime has to come up first (_lib.py)
-    nbytes = workspace_size(pairs, int(lens_a.max()), int(lens_b.max()))   # raises CHIRON_ERR_OVERFLOW before the GPU is touched
-    lib = _lib.load()
-    if not torch.cuda.is_available():
-        raise RuntimeError("chiron_amd.map.align_infix needs a GPU: the alignment has no CPU fallback")
-    dev = torch.device("cuda", device_id)
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    codes, lens_a, lens_b, read_off, win_off = _lib.pack_pairs(a, b)
+    lib, ws, stream = _lib.device_workspace(lambda: workspace_size(pairs, int(lens_a.max()), int(lens_b.max())), device_id,
+                                            "map.align_infix", "alignment")
     res = [np.zeros(pairs, dtype=np.int32) for _ in range(5)]
-    stream = torch.cuda.current_stream(dev)
     _lib.check(lib.chiron_align_infix(device_id, codes.ctypes.data, read_off.ctypes.data, win_off.ctypes.data, pairs, band0, 0,
                                       res[0].ctypes.data, res[1].ctypes.data, res[2].ctypes.data, res[3].ctypes.data,
-                                      res[4].ctypes.data, ws.data_ptr(), C.c_void_p(stream.cuda_stream)))
+                                      res[4].ctypes.data, ws.data_ptr(), stream))
     del ws
     out["edit"], out["match"], out["start"], out["end"], out["band"] = res
     return out

@@ -133,9 +133,7 @@ def from_map(result, reads, genome):
 # the kernel
 # ----------------------------------------------------------------------------------------------------------------------------
 def workspace_size(alignments, read_bytes, column_bytes, tile_len):
-    n = C.c_size_t()
-    _lib.check(_lib.load().chiron_pileup_workspace_size(alignments, read_bytes, column_bytes, tile_len, C.byref(n)))
-    return int(n.value)
+    return _lib.sized("chiron_pileup_workspace_size", alignments, read_bytes, column_bytes, tile_len)
 
 
 def pack(alignments):
@@ -162,19 +160,14 @@ def pileup_tile(alignments, g0, g1, ref_codes, min_depth, device_id=0, packed=No
     depth = np.zeros(tile, dtype=np.int32)
     call = np.zeros((tile, 8), dtype=np.uint8)
     clipped = C.c_int64()
-    import torch                                  # before the library loads: its ROCm runtime has to come up first (_lib.py)
+    import torch  # noqa: F401  before the library loads: its ROCm runtime has to come up first (_lib.py)
     nbytes = workspace_size(n, int(read_off[-1]), int(ops_off[-1]), tile)      # raises CHIRON_ERR_OVERFLOW before the GPU is touched
-    lib = _lib.load()
-    ws, ws_ptr, stream = None, None, None
+    lib, ws, stream = _lib.load(), None, None
     if tile > 0:                                  # the empty tile is validated on the host and touches no device
-        if not torch.cuda.is_available():
-            raise RuntimeError("chiron_amd.pileup.count needs a GPU: the pileup has no CPU fallback")
-        dev = torch.device("cuda", device_id)
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        ws_ptr, stream = ws.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        lib, ws, stream = _lib.device_workspace(nbytes, device_id, "pileup.count", "pileup")
     _lib.check(lib.chiron_pileup(device_id, codes.ctypes.data, read_off.ctypes.data, ops.ctypes.data, ops_off.ctypes.data, pos.ctypes.data, n,
                                  int(g0), int(g1), ref.ctypes.data if tile else None, min_depth, 0, counts.ctypes.data, depth.ctypes.data,
-                                 call.ctypes.data, C.byref(clipped), ws_ptr, stream))
+                                 call.ctypes.data, C.byref(clipped), ws.data_ptr() if tile else None, stream))
     del ws
     return counts, depth, call, int(clipped.value)
 
