@@ -28,6 +28,7 @@ CTC_WANT_GRAD, CTC_TRUSTED = 1, 2
 CTC_MAX_T, CTC_MAX_LABEL = 8192, 1 << 24
 ALIGN_MAX_LEN, ALIGN_BAND0, ALIGN_THREADS, ALIGN_LDS_SLOTS, ALIGN_MAX_GROUPS = 1 << 17, 256, 256, 4096, 2048
 INFIX_MAX_READ, INFIX_MAX_WINDOW, INFIX_BAND0, INFIX_THREADS, INFIX_LDS_SLOTS, INFIX_MAX_GROUPS = 1 << 17, (1 << 20) - 1, 256, 256, 4096, 2048
+SEED_K, SEED_BIN, SEED_THREADS, SEED_MAX_GROUPS, SEED_MAX_GENOME = 15, 256, 256, 2048, (1 << 31) - (1 << 18)
 LABEL_MAX_FRAMES, LABEL_MAX_BASES, LABEL_THREADS, LABEL_LDS_SLOTS, LABEL_MAX_GROUPS = 1 << 24, 1 << 22, 256, 4096, 1024
 PILEUP_INS_SLOTS, PILEUP_MAX_COLUMNS, PILEUP_MAX_TILE, PILEUP_THREADS = 4, 1 << 24, 1 << 28, 256
 PILEUP_PLANES = 6 + 5 * PILEUP_INS_SLOTS + 1
@@ -152,6 +153,9 @@ SYMBOLS = [
     ("chiron_align_infix_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     ("chiron_align_infix", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_seed_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    ("chiron_seed_reads", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("chiron_ctc_align_workspace_size", C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("chiron_ctc_align", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -210,7 +214,11 @@ def load():
         raise ImportError("%s has ABI version %s, this binding was written against %d: rebuild it "
                           "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, have, ABI_VERSION))
     for name, res, args in SYMBOLS:
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:                      # same version, older build: symbols are added without raising the version
+            raise ImportError("%s lacks %s, which this binding declares: rebuild it "
+                              "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, name))
         fn.restype = res
         fn.argtypes = args
     if (lib.chiron_build_flags() & BUILD_TIMING) and os.environ.get("CHIRON_ALLOW_TIMING_BUILD") != "1":

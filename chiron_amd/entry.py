@@ -7,6 +7,7 @@ import sys
 from os import path
 
 from . import __version__
+from .map import DEFAULT_SEED
 
 
 def set_paras(args, p):
@@ -201,7 +202,8 @@ def assess(args):
         from . import map as map_mod
         if args.reference:
             raise ValueError("assess: give the references with -r or a genome with -g, not both")
-        report = map_mod.assess_genome(args.input, args.genome, workspace_mb=args.workspace_mb, device_id=args.device, profile=args.profile)
+        report = map_mod.assess_genome(args.input, args.genome, workspace_mb=args.workspace_mb, device_id=args.device, profile=args.profile,
+                                       seed=getattr(args, "seed", DEFAULT_SEED))
     else:
         report = assess_mod.assess(args.input, args.reference, strand=args.strand, device_id=args.device, profile=args.profile,
                                    workspace_mb=args.workspace_mb)
@@ -219,12 +221,12 @@ def assess(args):
 
 
 def map_reads(args):
-    """Place called reads in a genome: map.map_command (k-mer votes on the host, exact infix alignment on the GPU).  Writes
+    """Place called reads in a genome: map.map_command (k-mer votes and exact infix alignment, both on the GPU).  Writes
     <out>/reference/<read>_ref.fasta (what `assess -r` and `label -r` take), <out>/mapped.paf and <out>/map_report.json; exits
     non-zero when no read mapped."""
     from . import map as map_mod
     report = map_mod.map_command(args.input, args.genome, args.output, min_votes=args.min_votes, max_occ=args.max_occ, band=args.band,
-                                 workspace_mb=args.workspace_mb, device_id=args.device, cigar=args.cigar)
+                                 workspace_mb=args.workspace_mb, device_id=args.device, cigar=args.cigar, seed=getattr(args, "seed", DEFAULT_SEED))
     t = report["totals"]
     print("map: %d reads; %d mapped, %d unmapped, %d at a window edge; identity of the mapped reads %.4f"
           % (t["reads"], t["mapped"], t["unmapped"], t["edge"], t["identity"]))
@@ -267,7 +269,8 @@ def label(args):
         from . import assess as assess_mod, map as map_mod
         if args.reference:
             raise ValueError("label: give the references with -r or a genome with -g, not both")
-        mapped = map_mod.map_reads(assess_mod.load_reads(args.input), map_mod.load_genome(args.genome), device_id=args.device)
+        mapped = map_mod.map_reads(assess_mod.load_reads(args.input), map_mod.load_genome(args.genome), device_id=args.device,
+                                   seeder=map_mod.seeder_of(getattr(args, "seed", DEFAULT_SEED), device_id=args.device))
         args.reference = path.join(args.output, "reference")
         map_mod.write_references(args.reference, mapped["references"])
     report = label_mod.label(args)
@@ -405,6 +408,9 @@ def build_parser():
     a.add_argument("--profile", action="store_true",
                    help="Also trace every pair on the GPU: the report gains each read's CIGAR (over =XID) and the pooled error profile "
                         "(substitution, insertion, deletion and homopolymer tables).")
+    a.add_argument("--seed", default=DEFAULT_SEED, choices=["gpu", "host"],
+                   help="Where the k-mer votes of the mapping are counted: on the GPU, or per read in numpy on the host (the reference; "
+                        "the results are the same).")
     a.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one traceback batch, MiB.")
     a.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     a.set_defaults(func=assess)
@@ -418,6 +424,9 @@ def build_parser():
     lb.add_argument("-g", "--genome", default=None,
                     help="A genome FASTA instead of -r: the called reads of -i (its result/) are mapped first (as `map` does) and the "
                          "stretches they cover are written to <output>/reference/ and used as the references.")
+    lb.add_argument("--seed", default=DEFAULT_SEED, choices=["gpu", "host"],
+                    help="Where the k-mer votes of the mapping are counted: on the GPU, or per read in numpy on the host (the reference; "
+                         "the results are the same).")
     lb.add_argument("-o", "--output", required=True, help="Folder the .signal/.label pairs and label_report.json are written to.")
     lb.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder path")
     lb.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
@@ -432,7 +441,7 @@ def build_parser():
     lb.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
                     help="Use seeded synthetic weights when the model folder has no checkpoint data.")
     lb.set_defaults(func=label)
-    mp = subparsers.add_parser("map", description="Place called reads in a genome: k-mer votes on the host, exact infix alignment of "
+    mp = subparsers.add_parser("map", description="Place called reads in a genome: k-mer votes, then exact infix alignment of "
                                "each read against its candidate window on the GPU",
                                help="Map called reads to a genome and cut out the per-read references.")
     mp.add_argument("-i", "--input", required=True, help="Output folder of `call` (its result/ is read), or a fasta/fastq file or folder.")
@@ -441,7 +450,10 @@ def build_parser():
     mp.add_argument("--min-votes", dest="min_votes", type=int, default=4, help="Fewest seed votes a read needs to be aligned at all.")
     mp.add_argument("--max-occ", dest="max_occ", type=int, default=64, help="K-mers that occur more often in the genome are not indexed.")
     mp.add_argument("--band", type=int, default=256, help="First half-width of the alignment band, in diagonals; 0: the full table.")
-    mp.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one alignment batch, MiB.")
+    mp.add_argument("--seed", default=DEFAULT_SEED, choices=["gpu", "host"],
+                    help="Where the k-mer votes of the mapping are counted: on the GPU, or per read in numpy on the host (the reference; "
+                         "the results are the same).")
+    mp.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one seeding or alignment batch, MiB.")
     mp.add_argument("--cigar", action="store_true",
                     help="Also trace every mapped read against the stretch it covers, in genome orientation: mapped.paf gains a cg:Z: "
                          "tag and mapped.sam is written.")

@@ -1,13 +1,13 @@
 """Read mapping: where in a genome does each called read lie, and which stretch of it does the read cover?
 
-`assess` and `label` need a reference sequence per read.  A run that has reads and a genome gets them here: seed on the host,
-align on the GPU (chiron_align_infix, csrc/map.hip), cut the covered stretch out.  `chiron map` writes the cut-outs as
+`assess` and `label` need a reference sequence per read.  A run that has reads and a genome gets them here: seed
+(chiron_seed_reads, csrc/seed.hip) and align (chiron_align_infix, csrc/map.hip) on the GPU, cut the covered stretch out.  `chiron map` writes the cut-outs as
 reference/<read>_ref.fasta, which `assess -r` and `label -r` take unchanged, a PAF file and a JSON report.  With `--cigar` every
 mapped read is also traced against the stretch it covers (assess.align_ops, csrc/trace.hip), in genome orientation: the PAF lines
 gain a cg:Z: tag and mapped.sam is written.
 
-Seeding is host-side numpy, deterministic and shared by the command and the tests, so a difference between the GPU and the
-reference can only come from the kernel:
+The seeding rule is host-side numpy (`vote`), deterministic and shared by the command and the tests; `vote_reads` is the same
+rule on the GPU, equal to it field for field, and what the commands run unless they are told `seed="host"`:
   genome   the contigs (assess.read_records, assess.encode) concatenated with runs of code 4 between them; a k-mer that holds a
            code 4 is never indexed, so none spans two contigs.
   index    k = 15, 2 bits per base; a stable argsort of the k-mer codes and their positions.  K-mers that occur more than
@@ -22,7 +22,7 @@ reference can only come from the kernel:
   window   [delta* - slack, delta* + n + slack) clipped to the contig, slack = max(256, n // 8).
   edge     a match that touches a window edge which is not a contig edge (s = 0, or e = m while the contig goes on) may continue
            outside: the read's slack doubles and it is aligned again in a follow-up launch, at most three times; then `edge`.
-There is no CPU fallback: without the library or a GPU, align_infix raises.
+There is no CPU fallback: without the library or a GPU, align_infix and vote_reads raise.
 """
 import json
 import os
@@ -215,6 +215,78 @@ def vote(index, read_codes, k=K):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
+# the votes on the GPU
+# ----------------------------------------------------------------------------------------------------------------------------
+SEEDS = ("gpu", "host")
+DEFAULT_SEED = "gpu"                    # what the commands run; "host" is the per-read numpy `vote`
+
+
+def seed_workspace_size(n_index, genome_len, reads, max_read, total_bases):
+    return _lib.sized("chiron_seed_workspace_size", n_index, genome_len, reads, max_read, total_bases)
+
+
+def plan_seed_batches(read_lens, n_index, genome_len, budget_bytes):
+    """Consecutive reads grouped so that each group's workspace stays within the budget (a single read always forms a group)."""
+    batches, cur, mr, total = [], [], 0, 0
+    for i, n in enumerate(read_lens):
+        nr, nt = max(mr, n), total + n
+        if cur and seed_workspace_size(n_index, genome_len, len(cur) + 1, nr, nt) > budget_bytes:
+            batches.append(cur)
+            cur, nr, nt = [], n, n
+        cur.append(i)
+        mr, total = nr, nt
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def seed_reads(idx_val, idx_pos, genome_len, reads, device_id=0):
+    """One call of chiron_seed_reads: idx_val uint32 and idx_pos int32 (sorted by value), reads a list of uint8 code arrays.
+    -> (votes, votes_second, strand as 0 / 1: int32 arrays; delta, g: int64 arrays)."""
+    count = len(reads)
+    lens = np.array([len(r) for r in reads], dtype=np.int64)
+    read_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    codes = np.ascontiguousarray(np.concatenate(list(reads) + [np.zeros(1, np.uint8)]))
+    res = [np.zeros(count, dtype=np.int32) for _ in range(3)] + [np.zeros(count, dtype=np.int64) for _ in range(2)]
+    if count == 0:
+        return res
+    lib, ws, stream = _lib.device_workspace(lambda: seed_workspace_size(len(idx_val), genome_len, count, int(lens.max()), int(lens.sum())),
+                                            device_id, "map.vote_reads", "seeding")
+    _lib.check(lib.chiron_seed_reads(device_id, idx_val.ctypes.data, idx_pos.ctypes.data, len(idx_val), genome_len, codes.ctypes.data,
+                                     read_off.ctypes.data, count, 0, *[r.ctypes.data for r in res], ws.data_ptr(), stream))
+    del ws
+    return res
+
+
+def vote_reads(index, reads, workspace_mb=4096, device_id=0):
+    """`vote` of every read, on the GPU: [vote(index, r) for r in reads], field for field.  The index goes to the device as
+    uint32 values and int32 positions; consecutive reads share a call while the call's workspace stays within workspace_mb."""
+    import torch  # noqa: F401  before the library loads: torch's ROCm runtime has to come up first (_lib.py)
+    idx_val, idx_pos = index
+    genome_len = int(idx_pos.max()) + K if len(idx_pos) else 0             # the shortest genome that holds every indexed k-mer
+    reads = [assess.encode(r) for r in reads]
+    lens = [len(r) for r in reads]
+    batches = plan_seed_batches(lens, len(idx_val), genome_len, int(workspace_mb * (1 << 20)))   # refuses an oversized genome first
+    val32, pos32 = np.ascontiguousarray(idx_val, dtype=np.uint32), np.ascontiguousarray(idx_pos, dtype=np.int32)
+    out = []
+    for batch in batches:
+        votes, second, strand, delta, g = seed_reads(val32, pos32, genome_len, [reads[i] for i in batch], device_id)
+        for v, s, w, d, at in zip(votes.tolist(), second.tolist(), strand.tolist(), delta.tolist(), g.tolist()):
+            out.append({"votes": v, "votes_second": s, "strand": "reverse" if w else "forward", "delta": d if v else None,
+                        "g": at if v else None})
+    return out
+
+
+def seeder_of(seed, workspace_mb=4096, device_id=0):
+    """The `seeder` of map_reads for a command's --seed: None (the per-read host `vote`) for "host", vote_reads for "gpu"."""
+    if seed not in SEEDS:
+        raise ValueError("seed must be one of %s, not %r" % (", ".join(SEEDS), seed))
+    if seed == "host":
+        return None
+    return lambda index, reads: vote_reads(index, reads, workspace_mb, device_id)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
 # the pipeline
 # ----------------------------------------------------------------------------------------------------------------------------
 def window_of(genome, contig, delta, n, slack):
@@ -227,10 +299,10 @@ def window_of(genome, contig, delta, n, slack):
 
 
 def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0, aligner=None,
-              seeds=None, index=None):
+              seeds=None, index=None, seeder=None):
     """Map {name: sequence} against a Genome.  aligner(reads, windows, band0) -> INFIX_DTYPE rows replaces the GPU kernel
     (the tests' reference pipeline); seeds {name: dict(strand, delta, contig)} replaces the voting for those reads (a test
-    hook).  -> dict(reads=[per-read records, name order], references={name: cut-out in the read's orientation}, totals,
+    hook); seeder(index, [codes]) -> [vote dicts] replaces the per-read host `vote` for the others (seeder_of).  -> dict(reads=[per-read records, name order], references={name: cut-out in the read's orientation}, totals,
     unmapped=[names])."""
     if aligner is None:
         def aligner(rs, ws, band0):
@@ -238,8 +310,11 @@ def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, w
     if index is None:
         index = build_index(genome.codes, K, max_occ)
     recs, todo = {}, []
-    for name in sorted(reads):
-        codes = assess.encode(reads[name])
+    coded = {name: assess.encode(reads[name]) for name in sorted(reads)}
+    voting = [name for name in coded if seeds is None or name not in seeds]
+    voted = dict(zip(voting, seeder(index, [coded[name] for name in voting]) if seeder is not None else
+                     (vote(index, coded[name]) for name in voting)))
+    for name, codes in coded.items():
         n = len(codes)
         rec = {"name": name, "read_len": n, "contig": None, "start": None, "end": None, "strand": None, "edit": None, "match": None,
                "mismatch": None, "insertion": None, "deletion": None, "identity": None, "votes": 0, "votes_second": 0, "band": None,
@@ -249,7 +324,7 @@ def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, w
             sd = seeds[name]
             strand, delta, contig = sd["strand"], int(sd["delta"]), int(sd["contig"])
         else:
-            v = vote(index, codes)
+            v = voted[name]
             rec["votes"], rec["votes_second"] = v["votes"], v["votes_second"]
             if v["votes"] < min_votes or v["delta"] is None:
                 continue
@@ -368,12 +443,14 @@ def write_outputs(out_dir, result, genome, meta=None, reads=None):
 
 
 def map_command(input_path, genome_path, out_dir, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0,
-                cigar=False):
-    """The `map` command: called reads + genome -> the three outputs (with cigar: traced, and mapped.sam too); returns the report."""
+                cigar=False, seed=DEFAULT_SEED):
+    """The `map` command: called reads + genome -> the three outputs (with cigar: traced, and mapped.sam too); returns the report.
+    seed: "gpu" votes with vote_reads, "host" with the per-read numpy `vote`; the outputs are the same."""
+    seeder = seeder_of(seed, workspace_mb, device_id)
     genome = load_genome(genome_path)
     reads = assess.load_reads(input_path)
-    result = map_reads(reads, genome, min_votes, max_occ, band, workspace_mb, device_id)
-    meta = {"input": input_path, "genome": genome_path, "k": K, "min_votes": min_votes, "max_occ": max_occ, "band": band}
+    result = map_reads(reads, genome, min_votes, max_occ, band, workspace_mb, device_id, seeder=seeder)
+    meta = {"input": input_path, "genome": genome_path, "k": K, "min_votes": min_votes, "max_occ": max_occ, "band": band, "seed": seed}
     if not cigar:
         return write_outputs(out_dir, result, genome, meta)
     add_cigars(result, reads, genome, workspace_mb, device_id)
@@ -381,13 +458,14 @@ def map_command(input_path, genome_path, out_dir, min_votes=MIN_VOTES, max_occ=M
 
 
 def assess_genome(input_path, genome_path, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0,
-                  profile=False):
+                  profile=False, seed=DEFAULT_SEED):
     """`assess -g`: map, then assess every mapped read against its cut-out (which is in the read's orientation, so the global
     alignment runs forward); the report's strand, contig, start and end come from the mapping.  Reads that did not map are the
     report's unpaired reads.  profile: the per-read cigar and the pooled error profile as well, in the read's orientation (not the
-    genome's, unlike `map --cigar`); the report's profile_orientation says so."""
+    genome's, unlike `map --cigar`); the report's profile_orientation says so.  seed: as for map_command."""
+    seeder = seeder_of(seed, workspace_mb, device_id)
     reads = assess.load_reads(input_path)
-    mapped = map_reads(reads, load_genome(genome_path), min_votes, max_occ, band, workspace_mb, device_id)
+    mapped = map_reads(reads, load_genome(genome_path), min_votes, max_occ, band, workspace_mb, device_id, seeder=seeder)
     paired, unpaired = assess.pair_reads(reads, mapped["references"])
     rows = assess.align_pairs([p[1] for p in paired], [p[2] for p in paired], device_id)
     by = {r["name"]: r for r in mapped["reads"]}

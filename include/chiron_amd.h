@@ -650,6 +650,51 @@ chiron_status chiron_align_infix(int32_t device_id, const uint8_t* codes, const 
                                  int32_t band0, uint32_t flags, int32_t* edit_out, int32_t* match_out, int32_t* start_out,
                                  int32_t* end_out, int32_t* band_out, void* workspace, void* stream);
 
+/* Seeding of the read mapper: where in a genome each read probably lies, from k-mer votes.  The index is the genome's k-mers of
+ * k = CHIRON_SEED_K bases, 2 bits a base with the first base highest, sorted by value: idx_val[i] the value, idx_pos[i] the
+ * position of the k-mer's first base in the (concatenated) genome, 0 <= idx_pos[i] <= genome_len - k; which k-mers it holds is the
+ * caller's choice.  Reads are codes 0..4.  Each read of n bases is scored as given (strand 0) and as its reverse complement
+ * (strand 1, the complement of code c < 4 is 3 - c); a k-mer that holds a code above 3 is skipped.  A hit of the k-mer at read
+ * position r on an index entry with position g votes for the diagonal delta = g - r, in bin floor(delta / CHIRON_SEED_BIN).  The
+ * score of a bin that holds a hit is its count plus the count of the next bin up.  The best score over both strands wins, ties to
+ * strand 0, then to the smaller bin beta: that score is votes_out and the strand strand_out.  second_out is the larger of the
+ * other strand's best score and the best score of a bin of the winning strand more than n / 256 + 2 bins from beta (0 without
+ * either).  The candidate (delta_out, g_out) is the hit of rank (votes - 1) / 2, counted from 0, among the hits of bins beta and
+ * beta + 1 of the winning strand ordered by (delta, g).  Without a hit votes_out and second_out are 0, strand_out is 0 and
+ * delta_out and g_out carry no meaning.  Every value is an integer sum, a maximum over a total order or a rank, so the result is
+ * a property of the inputs, and a read's result depends on that read alone.
+ *
+ * One workgroup of CHIRON_SEED_THREADS per read, read q on workgroup q mod the launch's group count (at most
+ * CHIRON_SEED_MAX_GROUPS); each k-mer is looked up once by binary search, the bins are counted with int32 atomic adds into a
+ * dense histogram per workgroup and strand, and the median is found by counting, not sorting (csrc/seed.hip).
+ *
+ * Workspace (device memory), each part rounded up to 256 bytes: the index (8 n_index bytes), total_bases + 1 bytes of codes, 16
+ * bytes of record and 20 of results a read, and for each of min(reads, CHIRON_SEED_MAX_GROUPS) workgroups 16 max_read bytes of
+ * looked-up k-mers and 8 ((genome_len + max_read rounded up to 256) / 256 + 2) bytes of counters.  Larger values of any argument
+ * are fine.  Host-only.  CHIRON_ERR_INVALID: a negative argument.  CHIRON_ERR_OVERFLOW: reads > 2^24, max_read >
+ * CHIRON_INFIX_MAX_READ, genome_len > CHIRON_SEED_MAX_GENOME (which keeps every delta and g in 32 bits with room for a read on
+ * either side), n_index > 2^31 - 1, total_bases > reads * CHIRON_INFIX_MAX_READ.                                                  */
+#define CHIRON_SEED_K 15
+#define CHIRON_SEED_BIN 256
+#define CHIRON_SEED_THREADS 256
+#define CHIRON_SEED_MAX_GROUPS 2048
+#define CHIRON_SEED_MAX_GENOME 0x7FFC0000   /* 2^31 - 2^18 */
+chiron_status chiron_seed_workspace_size(int64_t n_index, int64_t genome_len, int64_t reads, int64_t max_read, int64_t total_bases,
+                                         size_t* bytes);
+
+/* Seed `reads` reads in one launch.  idx_val (uint32) and idx_pos (int32): HOST [n_index], as above.  codes: HOST bytes; read q is
+ * codes[read_off[q] .. read_off[q+1]); read_off is HOST int64 [reads + 1], non-negative and non-decreasing.  votes_out,
+ * second_out, strand_out (0 forward, 1 reverse): HOST int32 [reads]; delta_out, g_out: HOST int64 [reads].  workspace: device
+ * memory on device_id of chiron_seed_workspace_size(n_index, genome_len, reads, longest read, sum of the reads) bytes.  flags: 0
+ * (reserved).  The call keeps no state: it copies the index and the reads in, runs on `stream` (a hipStream_t; NULL = the null
+ * stream) and synchronises it before returning.  CHIRON_ERR_INVALID for a null operand, unknown flags, a negative count, a bad
+ * offset, a code above 4, an index that is not sorted or holds a position outside 0 .. genome_len - k; CHIRON_ERR_OVERFLOW past
+ * the limits of the size function; all before anything is copied or launched.  reads == 0 is a no-op; n_index == 0 gives 0 votes
+ * for every read and touches no device.  CHIRON_ERR_STATE if the kernel finds its own counters inconsistent.                    */
+chiron_status chiron_seed_reads(int32_t device_id, const uint32_t* idx_val, const int32_t* idx_pos, int64_t n_index, int64_t genome_len,
+                                const uint8_t* codes, const int64_t* read_off, int64_t reads, uint32_t flags, int32_t* votes_out,
+                                int32_t* second_out, int32_t* strand_out, int64_t* delta_out, int64_t* g_out, void* workspace, void* stream);
+
 /* CTC forced alignment: given a read's frame scores and the bases it is known to have, the best monotone assignment of frames
  * to bases (what a resquiggler gives the reference project; here from the model's own logits).  Read r has frames
  * frame_off[r] .. frame_off[r+1]) of `scores`, float32 [frames, 5] with class 4 = blank, and bases label_off[r] .. label_off[r+1])

@@ -6,7 +6,10 @@ record:
   deletions, a third each), every other one reverse-complemented.
 
 Indexing (once), seeding (the votes of every read, host numpy) and alignment (map.align_in_batches on the windows the seeding
-chose: coding, packing, copies, the launches, synchronise) are timed separately with the host clock.  After one warm-up of the
+chose: coding, packing, copies, the launches, synchronise) are timed separately with the host clock.  The GPU seeding
+(map.vote_reads, chiron_seed_reads in csrc/seed.hip: the index conversion, packing, copies, the launch, synchronise, the Python
+dicts) is timed on the same reads and index in the same alternating rounds, after a warm-up of its own; its votes must equal the
+host's, and both times and their ratio are recorded.  After one warm-up of the
 alignment, the infix alignment and -- for context -- chiron_align_pairs on same-sized global pairs (each read against its window)
 alternate for --rounds rounds; medians are reported with the spread.  Band cells count every band a pair tried.  The numpy
 reference of tests/map_ref.py is timed on --baseline-pairs reads; its workload figure is the per-read mean times the number of
@@ -90,8 +93,15 @@ def main():
 
     first = cmap.align_in_batches(a, wins)                       # warm-up: code object load, allocator
     glob = assess.align_pairs(a, wins)
-    t_infix, t_glob = [], []
+    if cmap.vote_reads(index, reads) != votes:                   # warm-up of the seeding kernel, and its check
+        sys.exit("bench_map.py: the GPU votes differ from the host votes")
+    t_infix, t_glob, t_gpu_seed = [], [], []
     for _ in range(args.rounds):
+        t0 = time.perf_counter()
+        gpu_votes = cmap.vote_reads(index, reads)
+        t_gpu_seed.append(time.perf_counter() - t0)
+        if gpu_votes != votes:
+            sys.exit("bench_map.py: the GPU votes differ from the host votes")
         t0 = time.perf_counter()
         got = cmap.align_in_batches(a, wins)
         t_infix.append(time.perf_counter() - t0)
@@ -113,15 +123,19 @@ def main():
         if want != tuple(int(first[f][k]) for f in ("edit", "match", "start", "end")):
             sys.exit("bench_map.py: pair %d differs from the reference DP" % k)
     t = float(np.median(t_infix))
+    t_gs = float(np.median(t_gpu_seed))
     bands, band_counts = np.unique(first["band"], return_counts=True)
     tried, tried_counts = np.unique([c[2] for c in cells], return_counts=True)
     steps = sum((len(r) + len(w) + 1) * c[2] for r, w, c in zip(a, wins, cells))
     record = {
         "workload": {"reads": args.reads, "length": args.length, "genome": args.genome, "contigs": 2, "mutation_rate": args.rate,
                      "seed": 20241, "k": cmap.K, "max_occ": cmap.MAX_OCC, "band0": cmap.BAND0},
-        "timing": "host clock; index once, votes once, alignment %d rounds alternating with chiron_align_pairs after a warm-up" % args.rounds,
+        "timing": "host clock; index once, host votes once, GPU votes and alignment %d rounds alternating with chiron_align_pairs after a warm-up" % args.rounds,
         "device": torch.cuda.get_device_name(0),
         "index_seconds": t_index, "seeding_seconds": t_seed, "seeding_seconds_per_read": t_seed / max(len(reads), 1),
+        "seeding_gpu": {"what": "map.vote_reads on the same reads and index, equal to the host votes", "seconds_median": t_gs,
+                        "seconds_min": float(min(t_gpu_seed)), "seconds_max": float(max(t_gpu_seed)), "seconds_per_read": t_gs / max(len(reads), 1),
+                        "host_over_gpu": t_seed / t_gs},
         "reads_seeded": len(a), "reads_seeded_at_their_planted_place": placed,
         "align": {"pairs": len(a), "seconds_median": t, "seconds_min": float(min(t_infix)), "seconds_max": float(max(t_infix)),
                   "pairs_per_second": len(a) / t, "band_cell_updates_per_second": sum(c[0] for c in cells) / t,
@@ -132,6 +146,7 @@ def main():
                   "edit_over_read_len_mean": float(np.mean(first["edit"] / np.maximum([len(r) for r in a], 1)))},
         "host_share_of_map_time": (t_seed) / (t_seed + t),
         "host_share_with_indexing": (t_index + t_seed) / (t_index + t_seed + t),
+        "seeding_share_of_map_time_with_gpu_seeding": t_gs / (t_gs + t),
         "context_global_align_pairs": {"what": "chiron_align_pairs on the same pairs (read against its whole window, global)",
                                        "seconds_median": float(np.median(t_glob)), "pairs_per_second": len(a) / float(np.median(t_glob)),
                                        "accepted_band_distribution": {str(int(b)): int(c) for b, c in zip(*np.unique(glob["band"], return_counts=True))}},
