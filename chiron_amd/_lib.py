@@ -33,6 +33,7 @@ LABEL_MAX_FRAMES, LABEL_MAX_BASES, LABEL_THREADS, LABEL_LDS_SLOTS, LABEL_MAX_GRO
 PILEUP_INS_SLOTS, PILEUP_MAX_COLUMNS, PILEUP_MAX_TILE, PILEUP_THREADS = 4, 1 << 24, 1 << 28, 256
 PILEUP_PLANES = 6 + 5 * PILEUP_INS_SLOTS + 1
 PILEUP_CHUNK = 4 * PILEUP_THREADS    # columns a workgroup of csrc/pileup.hip loads before it scans them, 256 at a time
+PILEUP_MAX_GROUPS = 2048             # MAX_GROUPS of csrc/pileup.hip: workgroups of one launch, alignment p on workgroup p mod that
 
 
 class ResBlock(C.Structure):

@@ -9,6 +9,9 @@ non-negative, the packed (score, -bin) key, the pairwise prefix sum of rank_find
 ONE counter array over all the reads it takes and clears it by replaying the hits.  test_seed_cpu.py checks it against `vote`.
 
 `lookup` and `roll` are the kernel's index search and rolling k-mer loop in plain Python, checked there against numpy.
+
+long_read_cases() is the kernel at the read lengths it is made for, up to the 131072 bases it accepts.  Out of scope: genomes near
+SEED_MAX_GENOME.  An index of 2^31 positions is not a test-sized input.
 """
 import numpy as np
 
@@ -241,12 +244,15 @@ def hand_cases():
     return cases, extra
 
 
+HYGIENE_GENOME = 30000
+
+
 def hygiene_case(reads=2500):
     """More reads than workgroups against one 30 kb genome: 150 .. 400 bases, every third read its predecessor again, every seventh
     unrelated, the others cut from the genome at 5 % divergence, every other of those reverse-complemented."""
     from chiron_amd import assess, map as cmap
     rng = np.random.default_rng(4242)
-    g = assess_ref.random_seq(30000, rng)
+    g = assess_ref.random_seq(HYGIENE_GENOME, rng)
     out = []
     for k in range(reads):
         n = int(rng.integers(150, 401))
@@ -292,3 +298,46 @@ def random_case(rng):
         read = map_ref.revcomp(read)
     max_occ = int(rng.choice([2, 8, 64]))
     return cmap.build_index(cmap.Genome([("g", g)]).codes, cmap.K, max_occ), assess.encode(read)
+
+
+LONG_LENGTHS = (4095, 4096, 4097, 65535, 65536, 65537, 131072)
+_LONG = []
+
+
+def long_read_cases():
+    """One genome of 400 kb with one index, and reads of 4 k to 131072 bases (the longest the kernel takes), each on both strands:
+      cut<n>     cut from the genome at 8 % divergence, n bases, n around 2^12, around 2^16 and 2^17
+      tail_hit   70000 unrelated bases, then 3000 exact genome bases: every hit at read position >= 70000, so the candidate's
+                 256-position counter is number 273 or above, in the upper half of the 512
+      head_hit   the mirror image: counter 0 of a 73000-base read
+      unrelated  131072 bases that match nothing but by chance
+    The genome holds hygiene_case's 30 kb genome from position 185000 on, so that hygiene_case's short reads hit this index too
+    (mixed_batch).  -> (index, {name: codes}), built once: nobody changes them."""
+    if not _LONG:
+        from chiron_amd import assess, map as cmap
+        rng = np.random.default_rng(4343)
+        rs = assess_ref.random_seq
+        g = rs(185000, rng) + rs(HYGIENE_GENOME, np.random.default_rng(4242)) + rs(185000, rng)
+        seqs = {}
+        for k, n in enumerate(LONG_LENGTHS):
+            at = (15000 * k, 110000, 230000)[0 if n < 65000 else 1 if n < 131072 else 2]
+            piece = ""
+            while len(piece) < n:                                            # the mutation shortens or lengthens: cut generously, trim
+                piece = assess_ref.mutate(g[at:at + n + n // 20 + 400], 0.08, rng)
+            seqs["cut%d" % n] = piece[:n]
+        seqs["tail_hit"] = rs(70000, rng) + g[200000:203000]
+        seqs["head_hit"] = g[300000:303000] + rs(70000, rng)
+        seqs["unrelated"] = rs(131072, rng)
+        reads = {}
+        for name, seq in seqs.items():
+            reads[name] = assess.encode(seq)
+            reads[name + "_rc"] = assess.encode(map_ref.revcomp(seq))
+        _LONG.append((cmap.build_index(cmap.Genome([("g", g)]).codes), reads))
+    return _LONG[0]
+
+
+def mixed_batch(short=300):
+    """The 131072-base read cut from long_read_cases' genome and `short` of hygiene_case's reads, against that genome's index:
+    kc_stride, off and nbins of the call are sized by the long read.  -> (index, long read, [short reads])."""
+    index, reads = long_read_cases()
+    return index, reads["cut131072"], hygiene_case(short)[1]

@@ -124,6 +124,7 @@ def test_divergence_regimes_on_the_golden_reads(built):
 
 
 def test_batch_of_2048_is_deterministic_and_order_independent(built):
+    """One pair per workgroup.  The batch with more pairs than workgroups is tests/test_gpu_reuse.py's."""
     rng = np.random.default_rng(5)
     reads = [assess_ref.random_seq(int(rng.integers(300, 501)), rng) for _ in range(2048)]
     refs = [assess_ref.mutate(r, (0.05, 0.15, 0.4)[k % 3], rng) if k % 7 else assess_ref.random_seq(int(rng.integers(300, 501)), rng)

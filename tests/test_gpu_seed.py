@@ -80,6 +80,35 @@ def test_more_reads_than_workgroups_and_counter_hygiene(built, many):
     assert runs[0] == runs[1]
 
 
+@pytest.fixture(scope="module")
+def long_reads():
+    index, reads = seed_ref.long_read_cases()
+    codes = list(reads.values())
+    return index, codes, [cmap.vote(index, r) for r in codes]
+
+
+def test_long_reads_equal_vote(built, long_reads):
+    """4 k to 131072 bases, the longest read the kernel takes, on both strands: see seed_ref.long_read_cases."""
+    index, reads, want = long_reads
+    got = cmap.vote_reads(index, reads)
+    assert got == want
+    assert cmap.vote_reads(index, reads[::-1]) == want[::-1]
+    val32, pos32 = index[0].astype(np.uint32), index[1].astype(np.int32)
+    genome_len = int(index[1].max()) + cmap.K
+    runs = [b"".join(a.tobytes() for a in cmap.seed_reads(val32, pos32, genome_len, reads)) for _ in range(2)]
+    assert runs[0] == runs[1]
+
+
+def test_one_long_read_among_short_ones(built):
+    """The 131072-base read and 300 short reads in one call: the call's kc_stride, off and nbins are sized by the long read.
+    Every read's answer is the one it gets alone, with the long read first and with it last."""
+    index, long, short = seed_ref.mixed_batch()
+    alone = [cmap.vote_reads(index, [r])[0] for r in [long] + short]
+    assert alone == [cmap.vote(index, r) for r in [long] + short]
+    assert cmap.vote_reads(index, [long] + short) == alone
+    assert cmap.vote_reads(index, short + [long]) == alone[1:] + alone[:1]
+
+
 def test_batching_equals_one_call(built, many):
     index, reads, want = many
     reads, want = reads[:900], want[:900]

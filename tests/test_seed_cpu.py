@@ -100,6 +100,52 @@ def test_counters_stay_clean_over_many_reads_and_a_stale_one_would_show():
         assert stale["votes"] == 2 * want[2]["votes"]
 
 
+def test_scheme_equals_vote_at_long_reads_and_a_stale_counter_would_show():
+    """Reads of 4 k to 131072 bases: a thread's chunk of phase 1 far above 8 positions, phase 4's counters beyond the first eight
+    and, for tail_hit, beyond number 255, where rank_find passes thread 127's pair."""
+    from chiron_amd import _lib, map as cmap
+    index, reads = seed_ref.long_read_cases()
+    assert sorted({len(r) for r in reads.values()}) == [4095, 4096, 4097, 65535, 65536, 65537, 73000, _lib.INFIX_MAX_READ]
+    assert 390000 < len(index[0]) <= 400000
+    names, codes = list(reads), list(reads.values())
+    want = [cmap.vote(index, r) for r in codes]
+    by = dict(zip(names, want))
+    assert seed_ref.seed_all(index, codes) == want
+    for name in names:                                                       # the cases are what they claim to be
+        v, n = by[name], len(reads[name])
+        assert v["strand"] == ("reverse" if name.endswith("_rc") else "forward") or name.startswith("unrelated"), name
+        if name.startswith("cut"):
+            assert v["votes"] > n // 4 and v["votes_second"] < 10, (name, v)
+        elif name.startswith("unrelated"):
+            assert v["votes"] < 10, (name, v)
+        else:
+            assert v["votes"] == 3000 - cmap.K + 1 and v["votes_second"] < 10, (name, v)
+    tail, head = by["tail_hit"], by["head_hit"]
+    assert tail["g"] - tail["delta"] >= 65536 and (tail["g"] - tail["delta"]) // seed_ref.BIN >= 273      # the read position of the candidate
+    assert (head["g"] - head["delta"]) // seed_ref.BIN < 8
+    assert max(by[n]["g"] - by[n]["delta"] for n in names if n.startswith("cut")) // seed_ref.BIN >= 8
+    # one workgroup without its clearing pass: the second strand of a read meets the first one's counters
+    wg = seed_ref.Workgroup(index, max(len(r) for r in codes))
+    wrong = 0
+    for r, v in zip(codes, want):
+        try:
+            wrong += wg.seed(r, clear=False) != v
+        except AssertionError as e:
+            assert "stale" in str(e)
+            wrong += 1
+    assert wrong >= 1
+
+
+def test_the_mixed_batch_is_a_long_read_among_short_ones_that_hit():
+    from chiron_amd import _lib, map as cmap
+    index, long, short = seed_ref.mixed_batch()
+    assert len(long) == _lib.INFIX_MAX_READ and len(short) == 300 and max(len(r) for r in short) <= 450
+    want = [cmap.vote(index, r) for r in [long] + short]
+    assert seed_ref.seed_all(index, [long] + short) == want and seed_ref.seed_all(index, short + [long]) == want[1:] + want[:1]
+    assert sum(v["votes"] > 20 for v in want[1:]) > 200 and sum(v["votes"] == 0 for v in want[1:]) > 10
+    assert all(185000 - 400 <= v["delta"] <= 215000 for v in want[1:] if v["votes"] > 20)      # in the embedded 30 kb
+
+
 def _call(lib, idx_val, idx_pos, genome_len, codes, read_off, reads=None, flags=0, ws=1, n_index=None, nulls=()):
     val, pos = np.asarray(idx_val, np.uint32), np.asarray(idx_pos, np.int32)
     off, codes = np.asarray(read_off, np.int64), np.asarray(codes, np.uint8)
