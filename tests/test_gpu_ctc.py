@@ -1,8 +1,10 @@
 """GPU: the CTC loss / gradient kernels (chiron_ctc_loss) against the float64 restatement (tests/ctc_ref.py) and torch's float64
 autograd, the autograd Function, determinism, Engine.score (chiron_engine_score) after submit (greedy, beam), after
-chiron_engine_decode and on an RNA engine, and `validate` end to end."""
+chiron_engine_decode and on an RNA engine, the edit distance on truths of one to five 64-position words (tests/score_cases.py), the
+gradient on both sides of the 64 KB LDS opt-in, and `validate` end to end."""
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -13,6 +15,7 @@ import chiron_amd as ca
 from chiron_amd import ctc, labelled
 
 import ctc_ref
+import score_cases
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -159,7 +162,8 @@ def _labels_for(rng, n, Lmax=60):
     return rng.integers(0, 4, (n, Lmax)).astype(np.int32), ll
 
 
-def _check_score(eng, res, x_rows, sl, labels, ll, logits=None):
+def _check_score(eng, res, x_rows, sl, labels, ll, logits=None, want=None):
+    """want: the rows' normalized edit distances, for a caller that scores the same rows more than once (plain DP is slow)"""
     loss, edit, status = eng.score(0, labels, ll)
     ref_loss = ctc.ctc_loss(res.logits if logits is None else logits, sl, labels, ll)                       # the standalone kernel on the collected logits
     assert np.array_equal(loss.view(np.uint32), ref_loss.view(np.uint32))
@@ -170,7 +174,8 @@ def _check_score(eng, res, x_rows, sl, labels, ll, logits=None):
         flat, counts = res.compact.flat, res.compact.counts
         off = np.concatenate([[0], np.cumsum(counts)])
         rows = [list(flat[off[i]:off[i + 1]]) for i in range(x_rows)]
-    want = ctc.edit_distance(rows, labels, ll)
+    if want is None:
+        want = ctc.edit_distance(rows, labels, ll)
     assert np.array_equal(edit, want), (edit[:8], want[:8])
     return loss, edit, status
 
@@ -223,6 +228,80 @@ def test_engine_score_greedy_beam_decode(built):
         loss, edit, status = eng.score(0, tlab, tl)
         assert list(edit) == [0.0, np.float32(1) / np.float32(3), 0.5, 1.0, 0.25]
         assert np.array_equal(loss, ctc.ctc_loss(lg, dsl, tlab, tl))
+
+
+def test_engine_score_edit_distance_across_truth_words(built):
+    """edit_kernel on the rows of tests/score_cases.py: truths of 1 .. 320 positions (one to five 64-position words, exactly 64, 128,
+    192, 256 and 320 among them), hypotheses one or two edits away, empty hypotheses and truths, designed rows at the edges of the
+    kernel's 64-row blocks.  Bit for bit float32(d) / float32(m) with d from plain dynamic programming
+    (score_cases.normalized, held to ctc.levenshtein on these rows by tests/test_score_cases_cpu.py); then the same collected batch
+    against truths cut to 64 positions with max_label_len 64 and again at 320, so that the workspace stride changes between calls."""
+    rows = score_cases.edit_cases(400)
+    B = len(rows)
+    hyps = [hyp for _, hyp, _ in rows]
+    labels, ll = score_cases.dense_truths(rows)
+    assert labels.shape == (B, 320) and B > 128
+    want = score_cases.normalized(hyps, labels, ll)
+    claim = score_cases.claims(400)
+    for b, (name, hyp, truth) in enumerate(rows):
+        if truth:           # the designed distances, as far as the construction decides them
+            lo, hi = (np.float32(d) / np.float32(len(truth)) for d in claim[name])
+            assert lo <= want[b] <= hi, name
+    by_name = {name: b for b, (name, _, _) in enumerate(rows)}
+    assert np.isposinf(want[by_name["empty_truth"]]) and want[by_name["both_empty"]] == 0 and want[by_name["empty_hyp_m320"]] == 1
+    assert want[by_name["norepeat_del_first_m320"]] == np.float32(1) / np.float32(320)
+    labels64, ll64 = np.ascontiguousarray(labels[:, :64]), np.minimum(ll, 64)
+    want64 = score_cases.normalized(hyps, labels64, ll64)
+    spec = ca.dna_default_spec()
+    with ca.Engine(spec, ca.synthetic_weights(spec, seed=7), max_batch=B, segment_len=400) as eng:
+        assert eng.T == 400
+        lg = score_cases.greedy_logits(hyps, eng.T)
+        sl = np.full(B, eng.T, dtype=np.int32)
+        res = eng.decode(lg, sl, beam_width=0)
+        assert ctc.sparse_rows(res.decoded.indices, res.decoded.values, B) == hyps
+        for lab, n, w in ((labels, ll, want), (labels64, ll64, want64), (labels, ll, want)):
+            _, edit, _ = _check_score(eng, res, B, sl, lab, n, logits=lg, want=w)
+            assert edit.tobytes() == w.tobytes()
+
+
+def _lds_bytes(S):
+    """ctc_lds_bytes of csrc/ctc_loss.hip: the state row (S doubles), the frame's log-softmax (8 doubles), the extended label
+    (S bytes, rounded up to 8)"""
+    return (S + 8) * 8 + (S + 7) // 8 * 8
+
+
+@pytest.mark.parametrize("T", [3632, 3648])
+def test_gradient_on_both_sides_of_the_64k_lds_opt_in(built, T):
+    """ctc_beta_kernel with the last LDS size that needs no opt-in (T = Lmax = 3632: 65 456 bytes, the next multiple of 16 is past
+    64 KB) and the first size tested that needs it (3648: 65 744 bytes).  launch_ctc raises the limit of BOTH kernels; the loss
+    kernel alone runs above 64 KB elsewhere (test_loss_matches_float64 at T = 8192).  Rows: the longest feasible labels (no repeats,
+    one path), random labels of T / 2, a ragged row.  The alpha workspace is 3 * T * (2T + 1) doubles, about 0.64 GB."""
+    Lmax = T
+    S = 2 * min(Lmax, T) + 1
+    assert _lds_bytes(S) == {3632: 65456, 3648: 65744}[T]
+    assert _lds_bytes(2 * 3632 + 1) <= 64 * 1024 < _lds_bytes(2 * 3648 + 1)
+    with open(os.path.join(ROOT, "chiron_amd", "csrc", "ctc_loss.hip")) as f:
+        text = f.read()
+    assert re.search(r"size_t ctc_lds_bytes\(int S_lds\) \{ return \(\(size_t\)S_lds \+ 8\) \* sizeof\(double\) \+ "
+                     r"\(\(\(size_t\)S_lds \+ 7\) & ~\(size_t\)7\); \}", text)
+    assert re.search(r"if \(lds > 64 \* 1024\) \{\s*if \(hipFuncSetAttribute\([^;]*ctc_alpha_kernel[^;]*hipFuncSetAttribute\([^;]*ctc_beta_kernel", text)
+    assert re.search(r"p\.S_lds = S_ws;", text) and re.search(r"const int64_t S = 2 \* \(Lmax < T \? Lmax : T\) \+ 1;", text)
+    rng = np.random.default_rng(T)
+    B = 3
+    logits = rng.normal(scale=3.0, size=(B, T, 5)).astype(np.float32)
+    seq_len = np.array([T, T, T - 100], dtype=np.int32)
+    label_len = np.array([T, T // 2, 40], dtype=np.int32)
+    labels = np.zeros((B, Lmax), dtype=np.int32)
+    labels[0] = np.arange(T) % 4
+    labels[1, :T // 2] = rng.integers(0, 4, T // 2)
+    labels[2, :40] = rng.integers(0, 4, 40)
+    assert list(ctc.row_status(seq_len, labels, label_len)) == [0, 0, 0]
+    loss, grad = ctc.ctc_loss(logits, seq_len, labels, label_len, want_grad=True)
+    tl, tg = _torch_grad(logits, seq_len, labels, label_len)
+    assert np.isfinite(tl).all()
+    _check_loss(loss, tl)
+    assert np.abs(grad - tg).max() <= 1e-5, np.abs(grad - tg).max()
+    assert not grad[2, T - 100:].any() and grad[2, :T - 100].any()          # frames past seq_len are exactly 0
 
 
 def test_engine_score_rna(built):
