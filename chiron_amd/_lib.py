@@ -241,6 +241,13 @@ def sized(fn_name, *args):
     return int(n.value)
 
 
+def sized2(fn_name, *args):
+    """The two size_t values a host-only *_params_range / *_train_sizes function writes through its last two arguments."""
+    a, b = C.c_size_t(), C.c_size_t()
+    check(getattr(load(), fn_name)(*args, C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
 def pack_pairs(a, b):
     """uint8 code arrays a[p] and b[p] as chiron_align_pairs, _infix and _trace take them: every a, then every b, then one pad
     byte (the array is never empty).  -> (codes, lens_a, lens_b, off_a, off_b), the offsets into codes."""

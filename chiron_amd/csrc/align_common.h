@@ -7,10 +7,9 @@
 #include <stdint.h>
 
 #include "../../include/chiron_amd.h"
+#include "host_entry.h"
 
 namespace chiron {
-
-chiron_status set_error(chiron_status st, const char* fmt, ...);   // engine.hip
 
 // ---------------------------------------------------------------------------------------------
 // device: the band and its sweep
@@ -154,17 +153,8 @@ inline chiron_status pack_codes(const char* who, const char* item_a, const char*
 // The last refusals before the first copy: a workspace, a device to run on, and the workspace in that device's memory.
 inline chiron_status use_device_workspace(const char* who, int32_t device_id, const void* workspace) {
   if (!workspace) return set_error(CHIRON_ERR_INVALID, "%s: null workspace", who);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_DEVICE, "no HIP device %d: libchiron_amd has no CPU fallback", device_id);
-  }
-  if (hipSetDevice(device_id) != hipSuccess) return set_error(CHIRON_ERR_DEVICE, "hipSetDevice(%d) failed", device_id);
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, workspace) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_INVALID, "%s: workspace must be device memory on device %d", who, device_id);
-  }
+  if (chiron_status st = enter_device(nullptr, device_id)) return st;
+  if (!on_device(workspace)) return set_error(CHIRON_ERR_INVALID, "%s: workspace must be device memory on device %d", who, device_id);
   return CHIRON_OK;
 }
 

@@ -24,17 +24,15 @@
 // Every reduction over rows goes through per-slice partials whose slice count depends on the shape alone and a second pass in
 // slice order: no float atomics, the same bits run to run.
 #include "kernels.h"
+#include "model_layout.h"
 
 #include <cstdio>
 
 namespace chiron {
 
-chiron_status set_error(chiron_status st, const char* fmt, ...);   // engine.hip
-
 typedef float cg_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CT = 128, CK = 16, CLD = CT + 4;
-constexpr int CG_MAX_SITES = 1 + 4 * CHIRON_MAX_BLOCKS;
 constexpr int CG_RED_THREADS = 512;    // threads of a row-reduction workgroup: C / 4 channel lanes x row lanes
 constexpr int CG_SLICE_ROWS = 256;     // least rows per slice of a row reduction
 constexpr int CG_MAX_SLICES = 512;
@@ -493,10 +491,8 @@ __global__ __launch_bounds__(CG_RED_THREADS) void cg_rank1_dw_kernel(const CgRan
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct CgSite {
-  int ci, co, k, stride, pad, tin, tout;
-  bool bn, relu;
-  size_t w_off, bn_off;       // floats from the start of the CNN section
+struct CgSite : ConvSite {    // w_off / bn_off: the CNN section starts the blob, so they index params as they are
+  int pad, tin, tout;
   size_t y, r, stat;          // tape offsets (floats): convolution output, ReLU output (relu sites), statistics (bn sites)
   bool y_in_ws;               // the un-normalised shortcut lives in the workspace
   long rows;                  // B * tout
@@ -504,7 +500,7 @@ struct CgSite {
 
 struct CgLayout {
   int n_sites, n_blocks, has_stem;
-  CgSite s[CG_MAX_SITES];
+  CgSite s[MAX_SITES];
   int B, L, T, C;
   size_t n_params;
   size_t tape_floats;
@@ -520,42 +516,20 @@ static int cg_nsplit(long rows) {
   return (int)(n < 1 ? 1 : n > CG_DW_MAX_SPLIT ? CG_DW_MAX_SPLIT : n);
 }
 
-// TF 'SAME' padding: out = ceil(W / s), pad_total = max((out - 1) s + k - W, 0), left = total / 2
-static void cg_same_pad(int w, int k, int s, int* out, int* left) {
-  *out = (w + s - 1) / s;
-  int tot = (*out - 1) * s + k - w;
-  if (tot < 0) tot = 0;
-  *left = tot / 2;
-}
+// conv2c: what its r holds is the block's output
+static bool cg_block_out(const CgLayout& L, int site) { return site >= L.has_stem && (site - L.has_stem) % 4 == SITE_CONV2C; }
 
 static chiron_status cg_layout(const chiron_model_desc* d, int64_t batch, int64_t seg, bool want_shape, CgLayout* o) {
-  size_t total = 0;
-  chiron_status st = chiron_weights_size(d, &total);   // validates the descriptor
+  BlobMap map;
+  chiron_status st = blob_map(d, &map);
   if (st) return st;
   CgLayout& L = *o;
   L = CgLayout();
   L.n_blocks = d->n_blocks;
-  L.has_stem = d->stem_k > 0;
-  size_t n = 0;
-  int ns = 0;
-  auto add = [&](int ci, int co, int k, int stride, bool bn, bool relu) {
-    CgSite& s = L.s[ns++];
-    s.ci = ci; s.co = co; s.k = k; s.stride = stride; s.bn = bn; s.relu = relu;
-    s.w_off = n;
-    n += (size_t)k * ci * co;
-    s.bn_off = n;
-    if (bn) n += 4 * (size_t)co;
-  };
-  if (L.has_stem) add(1, d->stem_channels, d->stem_k, d->stem_stride, true, true);
-  for (int i = 0; i < d->n_blocks; ++i) {
-    const chiron_res_block& b = d->blocks[i];
-    add(b.in_channels, b.out_channels, 1, b.stride, b.i_bn != 0, false);
-    add(b.in_channels, b.out_channels, 1, 1, true, true);
-    add(b.out_channels, b.out_channels, b.k, b.stride, true, true);
-    add(b.out_channels, b.out_channels, 1, 1, true, false);
-  }
-  L.n_sites = ns;
-  L.n_params = n;
+  L.has_stem = map.has_stem;
+  const int ns = L.n_sites = map.n_sites;
+  for (int i = 0; i < ns; ++i) static_cast<ConvSite&>(L.s[i]) = map.site[i];
+  L.n_params = map.cnn_floats;
   L.C = d->blocks[d->n_blocks - 1].out_channels;
   for (int i = 0; i < ns; ++i) {
     if (L.s[i].co > 4 * CG_RED_THREADS) return set_error(CHIRON_ERR_INVALID, "the CNN training kernels take at most %d channels, not %d", 4 * CG_RED_THREADS, L.s[i].co);
@@ -567,29 +541,19 @@ static chiron_status cg_layout(const chiron_model_desc* d, int64_t batch, int64_
     return set_error(CHIRON_ERR_OVERFLOW, "batch %lld x segment_len %lld beyond the training kernels' range (batch 2^20, 2^24 rows)", (long long)batch, (long long)seg);
   L.B = (int)batch;
   L.L = (int)seg;
-  int t = (int)seg;
-  int si = 0;
+  SiteFrames fr[MAX_SITES];
+  const int t = L.T = frames(map, (int)seg, fr);
   size_t f = 0, big = 0;
-  auto place = [&](CgSite& s, int tin, bool block_out) {
-    s.tin = tin;
-    cg_same_pad(tin, s.k, s.stride, &s.tout, &s.pad);
+  for (int i = 0; i < ns; ++i) {
+    CgSite& s = L.s[i];
+    s.tin = fr[i].tin; s.tout = fr[i].tout; s.pad = fr[i].pad;
     s.rows = (long)L.B * s.tout;
     const size_t act = (size_t)s.rows * s.co;
     if (act > big) big = act;
     s.y_in_ws = !s.bn;
     if (s.bn) { s.y = f; f += act; s.stat = f; f += 4 * (size_t)s.co; }
-    if (s.relu || block_out) { s.r = f; f += act; }
-  };
-  if (L.has_stem) { place(L.s[si], t, false); t = L.s[si].tout; ++si; }
-  for (int i = 0; i < d->n_blocks; ++i) {
-    place(L.s[si], t, false);          // branch1
-    place(L.s[si + 1], t, false);      // conv2a
-    place(L.s[si + 2], t, false);      // conv2b
-    t = L.s[si + 2].tout;
-    place(L.s[si + 3], t, true);       // conv2c; its r is the block's output
-    si += 4;
+    if (s.relu || cg_block_out(L, i)) { s.r = f; f += act; }
   }
-  L.T = t;
   if (t > CHIRON_CTC_MAX_T) return set_error(CHIRON_ERR_OVERFLOW, "%d frames: the training kernels take at most %d", t, CHIRON_CTC_MAX_T);
   L.tape_floats = f;
   f = 0;
@@ -605,23 +569,6 @@ static chiron_status cg_layout(const chiron_model_desc* d, int64_t batch, int64_
   L.part = f; f += part;
   L.sums = f; f += 2 * (size_t)(4 * CG_RED_THREADS);
   L.ws_floats = f;
-  return CHIRON_OK;
-}
-
-static bool cg_device_ptr(const void* p) {
-  hipPointerAttribute_t a;
-  const bool ok = p && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice;
-  if (!ok) (void)hipGetLastError();
-  return ok;
-}
-
-static chiron_status cg_enter(const char* who, int32_t device_id) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_DEVICE, "%s: no HIP device %d: libchiron_amd has no CPU fallback", who, device_id);
-  }
-  if (hipSetDevice(device_id) != hipSuccess) return set_error(CHIRON_ERR_DEVICE, "%s: hipSetDevice(%d) failed", who, device_id);
   return CHIRON_OK;
 }
 
@@ -712,12 +659,6 @@ static void cg_bn_backward(const CgSite& s, const float* din, const float* relu_
   hipLaunchKernelGGL(cg_bn_bwd_apply_kernel, dim3(cg_grid(p.n4, 256)), dim3(256), 0, stream, p);
 }
 
-static chiron_status cg_launched(const char* who) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(CHIRON_ERR_DEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return CHIRON_OK;
-}
-
 }  // namespace chiron
 
 using namespace chiron;
@@ -752,8 +693,7 @@ extern "C" chiron_status chiron_cnn_train_tape_relu(const chiron_model_desc* des
   int seen = 0;
   for (int i = 0; i < L.n_sites; ++i) {
     const CgSite& s = L.s[i];
-    const bool block_out = (i - L.has_stem) % 4 == 3 && i >= L.has_stem;
-    if (!(s.relu || block_out)) continue;
+    if (!(s.relu || cg_block_out(L, i))) continue;
     if (seen++ == index) {
       *offset_floats = s.r;
       *frames = s.tout;
@@ -772,9 +712,9 @@ extern "C" chiron_status chiron_cnn_train_forward(int32_t device_id, const chiro
   chiron_status st = cg_layout(desc, batch, segment_len, true, &L);
   if (st) return st;
   if (!params || !signal || !features_out || !moments_out || !tape_ || !workspace_) return set_error(CHIRON_ERR_INVALID, "%s: null operand", who);
-  if ((st = cg_enter(who, device_id))) return st;
-  if (!(cg_device_ptr(params) && cg_device_ptr(signal) && cg_device_ptr(features_out) && cg_device_ptr(moments_out) && cg_device_ptr(tape_) &&
-        cg_device_ptr(workspace_)))
+  if ((st = enter_device(who, device_id))) return st;
+  if (!(on_device(params) && on_device(signal) && on_device(features_out) && on_device(moments_out) && on_device(tape_) &&
+        on_device(workspace_)))
     return set_error(CHIRON_ERR_INVALID, "%s: every operand must be device memory on device %d", who, device_id);
   hipStream_t stream = (hipStream_t)stream_;
   float* tape = (float*)tape_;
@@ -812,7 +752,7 @@ extern "C" chiron_status chiron_cnn_train_forward(int32_t device_id, const chiro
     apply(c, conv(c, tape + b.r), y1, b1.bn ? tape + b1.stat : nullptr, i == L.n_blocks - 1 ? features_out : nullptr);
     x = tape + c.r;
   }
-  return cg_launched(who);
+  return launched(who);
 }
 
 extern "C" chiron_status chiron_cnn_train_backward(int32_t device_id, const chiron_model_desc* desc, const float* params, const float* signal,
@@ -823,9 +763,9 @@ extern "C" chiron_status chiron_cnn_train_backward(int32_t device_id, const chir
   chiron_status st = cg_layout(desc, batch, segment_len, true, &L);
   if (st) return st;
   if (!params || !signal || !dfeatures || !tape_ || !workspace_ || !dparams_out) return set_error(CHIRON_ERR_INVALID, "%s: null operand", who);
-  if ((st = cg_enter(who, device_id))) return st;
-  if (!(cg_device_ptr(params) && cg_device_ptr(signal) && cg_device_ptr(dfeatures) && cg_device_ptr(tape_) && cg_device_ptr(workspace_) &&
-        cg_device_ptr(dparams_out)))
+  if ((st = enter_device(who, device_id))) return st;
+  if (!(on_device(params) && on_device(signal) && on_device(dfeatures) && on_device(tape_) && on_device(workspace_) &&
+        on_device(dparams_out)))
     return set_error(CHIRON_ERR_INVALID, "%s: every operand must be device memory on device %d", who, device_id);
   hipStream_t stream = (hipStream_t)stream_;
   const float* tape = (const float*)tape_;
@@ -862,5 +802,5 @@ extern "C" chiron_status chiron_cnn_train_backward(int32_t device_id, const chir
     cg_bn_backward(s, dcur, tape + s.r, tape, params, dparams_out, part, sums, Q, nullptr, stream);
     cg_conv_dw(s, signal, Q, part, dparams_out + s.w_off, stream);
   }
-  return cg_launched(who);
+  return launched(who);
 }

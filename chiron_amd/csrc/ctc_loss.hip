@@ -24,10 +24,10 @@
 #include <vector>
 
 #include "../../include/chiron_amd.h"
+#include "host_entry.h"
 #include "kernels.h"
 
 namespace chiron {
-chiron_status set_error(chiron_status st, const char* fmt, ...);
 
 namespace {
 
@@ -408,13 +408,6 @@ static chiron_status read_ints(const int32_t* p, size_t n, hipStream_t stream, s
   return CHIRON_OK;
 }
 
-static bool is_device_ptr(const void* p) {
-  hipPointerAttribute_t a;
-  const bool ok = hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice;
-  if (!ok) (void)hipGetLastError();
-  return ok;
-}
-
 extern "C" chiron_status chiron_ctc_loss(int32_t device_id, const float* logits, const int32_t* seq_len, const int32_t* labels,
                                          const int32_t* label_len, int32_t batch, int32_t T, int32_t max_label_len, uint32_t flags,
                                          float* loss_out, float* grad_out, void* workspace, void* stream_) {
@@ -436,9 +429,9 @@ extern "C" chiron_status chiron_ctc_loss(int32_t device_id, const float* logits,
   (void)hipGetLastError();
   bool d_seq = false, d_len = false, d_lab = false;
   if (flags & CHIRON_CTC_TRUSTED) {   // no read-back, no synchronisation: the kernels clamp what they index with
-    d_seq = is_device_ptr(seq_len);
-    d_len = is_device_ptr(label_len);
-    d_lab = max_label_len == 0 || is_device_ptr(labels);
+    d_seq = on_device(seq_len);
+    d_len = on_device(label_len);
+    d_lab = max_label_len == 0 || on_device(labels);
   } else {
     std::vector<int32_t> h_seq, h_len, h_lab;
     if ((st = read_ints(seq_len, (size_t)batch, stream, h_seq, &d_seq))) return st;
@@ -447,8 +440,8 @@ extern "C" chiron_status chiron_ctc_loss(int32_t device_id, const float* logits,
     if ((st = ctc_check_rows(h_seq.data(), h_lab.data(), h_len.data(), batch, T, max_label_len))) return st;
   }
   if (!have_gpu) return set_error(CHIRON_ERR_DEVICE, "no HIP device %d: libchiron_amd has no CPU fallback", device_id);
-  if (!(d_seq && d_len && (d_lab || max_label_len == 0) && is_device_ptr(logits) && is_device_ptr(loss_out) &&
-        (!grad || (is_device_ptr(grad_out) && is_device_ptr(workspace)))))
+  if (!(d_seq && d_len && (d_lab || max_label_len == 0) && on_device(logits) && on_device(loss_out) &&
+        (!grad || (on_device(grad_out) && on_device(workspace)))))
     return set_error(CHIRON_ERR_INVALID, "chiron_ctc_loss: every operand must be device memory on device %d", device_id);
   CtcParams p;
   p.logits = logits;

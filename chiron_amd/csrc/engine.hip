@@ -19,6 +19,7 @@
 
 #include "../../include/chiron_amd.h"
 #include "kernels.h"
+#include "model_layout.h"
 #include <dlfcn.h>
 
 // profiling buckets (chiron_engine_profile_read) = names of the roctx ranges (CHIRON_ROCTX); order = the PN_* enum below
@@ -31,21 +32,6 @@ using namespace chiron;
 // error plumbing: never throw across the ABI
 // ----------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static chiron_status fail(chiron_status st, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return st;
-}
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess)                                                                          \
-      return fail(CHIRON_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
-                  __LINE__);                                                                       \
-  } while (0)
-
 namespace chiron {
 chiron_status set_error(chiron_status st, const char* fmt, ...) {
   va_list ap;
@@ -55,6 +41,14 @@ chiron_status set_error(chiron_status st, const char* fmt, ...) {
   return st;
 }
 }  // namespace chiron
+static constexpr auto& fail = chiron::set_error;   // this file's name for it
+#define HIP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess)                                                                          \
+      return fail(CHIRON_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, \
+                  __LINE__);                                                                       \
+  } while (0)
 
 extern "C" const char* chiron_last_error(void) { return g_err; }
 extern "C" int32_t chiron_abi_version(void) { return CHIRON_ABI_VERSION; }
@@ -85,61 +79,12 @@ extern "C" chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, 
 
 static int roundup(int v, int m) { return (v + m - 1) / m * m; }
 
-// TF 'SAME' padding: out = ceil(W/s), pad_total = max((out-1)s + k - W, 0), left = total/2
-static void same_pad(int w, int k, int s, int* out, int* left) {
-  *out = (w + s - 1) / s;
-  int tot = (*out - 1) * s + k - w;
-  if (tot < 0) tot = 0;
-  *left = tot / 2;
-}
-
-// ----------------------------------------------------------------------------------------------
-// model description helpers
-// ----------------------------------------------------------------------------------------------
-static chiron_status validate_desc(const chiron_model_desc* d) {
-  if (!d) return fail(CHIRON_ERR_INVALID, "null model descriptor");
-  if (d->n_blocks < 1 || d->n_blocks > CHIRON_MAX_BLOCKS) return fail(CHIRON_ERR_INVALID, "n_blocks %d out of range", d->n_blocks);
-  for (int i = 0; i < d->n_blocks; ++i) {
-    const chiron_res_block& b = d->blocks[i];
-    const int want_in = i == 0 ? (d->stem_k > 0 ? d->stem_channels : 1) : d->blocks[i - 1].out_channels;
-    if (b.in_channels != want_in) return fail(CHIRON_ERR_INVALID, "block %d: in_channels %d, expected %d", i, b.in_channels, want_in);
-    if (b.out_channels < 4 || b.out_channels % 4) return fail(CHIRON_ERR_INVALID, "block %d: out_channels must be a multiple of 4", i);
-    if (b.k < 1 || b.k > GEMM_MAX_SEG) return fail(CHIRON_ERR_INVALID, "block %d: conv2b width %d unsupported (1..%d)", i, b.k, GEMM_MAX_SEG);
-    if (b.stride < 1) return fail(CHIRON_ERR_INVALID, "block %d: stride %d", i, b.stride);
-  }
-  if (d->stem_k < 0 || d->stem_k > 64 || (d->stem_k > 0 && (d->stem_stride < 1 || d->stem_channels < 8 || d->stem_channels % 8)))
-    return fail(CHIRON_ERR_INVALID, "stem: k %d stride %d channels %d", d->stem_k, d->stem_stride, d->stem_channels);
-  if (d->rnn_kind != CHIRON_RNN_STACK && d->rnn_kind != CHIRON_RNN_MULTI) return fail(CHIRON_ERR_INVALID, "rnn_kind %d", d->rnn_kind);
-  if (d->rnn_layers < 1 || d->rnn_layers > 8) return fail(CHIRON_ERR_INVALID, "rnn_layers %d unsupported (1..8)", d->rnn_layers);
-  if (d->hidden < 4 || d->hidden > 100 || d->hidden % 4) return fail(CHIRON_ERR_INVALID, "hidden %d unsupported (multiple of 4, <= 100)", d->hidden);
-  if (d->classes < 2 || d->classes > CHIRON_KMAX) return fail(CHIRON_ERR_INVALID, "classes %d unsupported (2..%d)", d->classes, CHIRON_KMAX);
-  if (d->bn_mode != CHIRON_BN_POPULATION && d->bn_mode != CHIRON_BN_BATCH) return fail(CHIRON_ERR_INVALID, "bn_mode %d", d->bn_mode);
-  return CHIRON_OK;
-}
-
-static int lstm_in_width(const chiron_model_desc* d, int layer) {
-  if (layer == 0) return d->blocks[d->n_blocks - 1].out_channels;
-  return d->rnn_kind == CHIRON_RNN_STACK ? 2 * d->hidden : d->hidden;
-}
-
 extern "C" chiron_status chiron_weights_size(const chiron_model_desc* d, size_t* n_floats) {
-  chiron_status st = validate_desc(d);
+  BlobMap map;
+  chiron_status st = blob_map(d, &map);
   if (st) return st;
   if (!n_floats) return fail(CHIRON_ERR_INVALID, "null n_floats");
-  size_t n = 0;
-  if (d->stem_k > 0) n += (size_t)d->stem_k * d->stem_channels + 4 * (size_t)d->stem_channels;
-  for (int i = 0; i < d->n_blocks; ++i) {
-    const chiron_res_block& b = d->blocks[i];
-    const size_t ci = b.in_channels, co = b.out_channels;
-    n += ci * co + (b.i_bn ? 4 * co : 0);  // branch1
-    n += ci * co + 4 * co;                 // conv2a
-    n += (size_t)b.k * co * co + 4 * co;   // conv2b
-    n += co * co + 4 * co;                 // conv2c
-  }
-  const size_t H = d->hidden;
-  for (int l = 0; l < d->rnn_layers; ++l) n += 2 * ((lstm_in_width(d, l) + H) * 4 * H + 4 * H);
-  n += 2 * H + H + H * d->classes + d->classes;
-  *n_floats = n;
+  *n_floats = map.total;
   return CHIRON_OK;
 }
 
@@ -294,6 +239,7 @@ struct Slot {
 
 struct chiron_engine {
   chiron_model_desc desc;
+  BlobMap map;                    // where desc puts every tensor of the weight blob
   chiron_engine_opts opts;
   int L = 0, T = 0, C = 0, H = 0, K = 0;
   int maxB = 0, BP = 0;
@@ -325,7 +271,6 @@ struct chiron_engine {
   std::vector<Slot> slots;
   std::map<const float*, PlanHost> plan_host;   // f16 engine: keyed by the plan's device shift pointer
   std::vector<float> host_weights;              // f16 engine: the caller's blob (LSTM kernels are read back from it in calibration)
-  std::vector<size_t> lstm_kernel_off[2];       // offset of layer l's kernel of direction d in host_weights
   CalibCtx* calib = nullptr;                    // non-null while chiron_engine_calibrate runs the network
   int calibrated = 0;                           // iterations applied so far
   std::vector<void*> owned;  // device allocations freed on destroy
@@ -435,93 +380,83 @@ static chiron_status upload_gemm(chiron_engine* e, ConvGemmPlan* g, const std::v
   return dev_upload(e, &g->shift, shift);
 }
 
-static chiron_status build_plans(chiron_engine* e, const float* w) {
+// Stem and residual blocks: BN folded into (population) or kept beside (batch) the weights, in the layouts the convolution kernels read
+static chiron_status plan_stem_and_blocks(chiron_engine* e, const float* w) {
   const chiron_model_desc& d = e->desc;
-  const bool batch = d.bn_mode == CHIRON_BN_BATCH;
-  e->bn_batch = batch;
-  if (batch && (e->f16 || e->split)) return fail(CHIRON_ERR_INVALID, "bn_mode=batch is implemented for dtype f32 only");
-  if (e->f16 || e->split) {
-    for (int bi = 0; bi < d.n_blocks; ++bi)
-      if (d.blocks[bi].out_channels % GEMM_BN || (d.blocks[bi].in_channels != 1 && d.blocks[bi].in_channels % 64))
-        return fail(CHIRON_ERR_INVALID, "dtype f16: block %d has %d -> %d channels; the f16 kernels need multiples of 64 / 128", bi,
-                    d.blocks[bi].in_channels, d.blocks[bi].out_channels);
-  }
-  int t = e->L;
-  const float* p = w;
-  if (d.stem_k > 0) {
-    const int k = d.stem_k, co = d.stem_channels;
-    const float* Ws = p;  // [k][1][co]
-    p += (size_t)k * co;
+  const BlobMap& map = e->map;
+  const bool batch = e->bn_batch;
+  SiteFrames fr[MAX_SITES];
+  e->T = frames(map, e->L, fr);
+  e->C = d.blocks[d.n_blocks - 1].out_channels;
+  if (map.has_stem) {
+    const ConvSite& s = map.site[0];
+    const int k = s.k, co = s.co;
+    const float *Ws = w + s.w_off, *bn = w + s.bn_off;  // [k][1][co]
     std::vector<float> wf((size_t)k * co), sh(co, 0.f);
     chiron_status st;
     if (batch) {
-      std::vector<float> sc(p, p + co), of(p + co, p + 2 * co);
+      std::vector<float> sc(bn, bn + co), of(bn + co, bn + 2 * co);
       for (size_t i = 0; i < wf.size(); ++i) wf[i] = Ws[i];
       if ((st = dev_upload(e, &e->stem_scale, sc))) return st;
       if ((st = dev_upload(e, &e->stem_offset, of))) return st;
     } else {
-      const BnFold f = fold_bn(p, p + co, p + 2 * co, p + 3 * co, co);
+      const BnFold f = fold_bn(bn, bn + co, bn + 2 * co, bn + 3 * co, co);
       for (int tap = 0; tap < k; ++tap)
         for (int c = 0; c < co; ++c) wf[(size_t)tap * co + c] = Ws[(size_t)tap * co + c] * f.inv[c];
       sh = f.sh;
     }
-    p += 4 * co;
     if ((st = dev_upload(e, &e->stem_w, wf))) return st;
     if ((st = dev_upload(e, &e->stem_shift, sh))) return st;
     e->stem_k = k;
-    e->stem_stride = d.stem_stride;
+    e->stem_stride = s.stride;
     e->stem_c = co;
-    same_pad(t, k, d.stem_stride, &e->stem_t, &e->stem_left);
-    t = e->stem_t;
+    e->stem_t = fr[0].tout;
+    e->stem_left = fr[0].pad;
   }
   for (int bi = 0; bi < d.n_blocks; ++bi) {
     const chiron_res_block& b = d.blocks[bi];
+    const ConvSite* site = map.site + map.has_stem + 4 * bi;   // site[SITE_BRANCH1 .. SITE_CONV2C]
+    const SiteFrames& f2 = fr[map.has_stem + 4 * bi + SITE_CONV2B];
     BlockPlan bp;
     bp.lift = b.in_channels == 1;
     bp.c_in = b.in_channels;
     bp.c = b.out_channels;
     bp.k = b.k;
     bp.stride = b.stride;
-    bp.t_in = t;
-    same_pad(t, b.k, b.stride, &bp.t_out, &bp.left);
+    bp.t_in = f2.tin;
+    bp.t_out = f2.tout;
+    bp.left = f2.pad;
+    const int t = bp.t_in;
     const int ci = b.in_channels, co = b.out_channels;
     chiron_status st;
     bp.i_bn = b.i_bn != 0;
     // one BN site: population statistics fold into the weights; batch statistics leave the weights raw and keep
     // scale / offset for bn_batch.hip
-    auto bn_site = [&](int site, BnFold* f) -> chiron_status {
+    auto bn_site = [&](int which, BnFold* f) -> chiron_status {
+      const float* bn = w + site[which].bn_off;
       if (batch) {
         f->inv.assign(co, 1.0f);
         f->sh.assign(co, 0.0f);
-        std::vector<float> sc(p, p + co), of(p + co, p + 2 * co);
-        chiron_status r = dev_upload(e, &bp.bn_scale[site], sc);
-        if (r == CHIRON_OK) r = dev_upload(e, &bp.bn_offset[site], of);
-        p += 4 * co;
+        std::vector<float> sc(bn, bn + co), of(bn + co, bn + 2 * co);
+        chiron_status r = dev_upload(e, &bp.bn_scale[which], sc);
+        if (r == CHIRON_OK) r = dev_upload(e, &bp.bn_offset[which], of);
         return r;
       }
-      *f = fold_bn(p, p + co, p + 2 * co, p + 3 * co, co);
-      p += 4 * co;
+      *f = fold_bn(bn, bn + co, bn + 2 * co, bn + 3 * co, co);
       return CHIRON_OK;
     };
-    const float* W1 = p;
-    p += (size_t)ci * co;
-    BnFold f1;
+    const float *W1 = w + site[SITE_BRANCH1].w_off, *W2a = w + site[SITE_CONV2A].w_off, *W2b = w + site[SITE_CONV2B].w_off,
+                *W2c = w + site[SITE_CONV2C].w_off;
+    BnFold f1, f2a, f2b, f2c;
     if (b.i_bn) {
-      if ((st = bn_site(0, &f1))) return st;
+      if ((st = bn_site(SITE_BRANCH1, &f1))) return st;
     } else {
       f1.inv.assign(co, 1.0f);
       f1.sh.assign(co, 0.0f);
     }
-    const float* W2a = p;
-    p += (size_t)ci * co;
-    BnFold f2a, f2b, f2c;
-    if ((st = bn_site(1, &f2a))) return st;
-    const float* W2b = p;
-    p += (size_t)b.k * co * co;
-    if ((st = bn_site(2, &f2b))) return st;
-    const float* W2c = p;
-    p += (size_t)co * co;
-    if ((st = bn_site(3, &f2c))) return st;
+    if ((st = bn_site(SITE_CONV2A, &f2a))) return st;
+    if ((st = bn_site(SITE_CONV2B, &f2b))) return st;
+    if ((st = bn_site(SITE_CONV2C, &f2c))) return st;
 
     const int Npad = roundup(co, GEMM_BN);
     const int cop = roundup(co, e->kq);
@@ -672,125 +607,69 @@ static chiron_status build_plans(chiron_engine* e, const float* w) {
       }
     }
     e->blocks.push_back(bp);
-    t = bp.t_out;
   }
-  e->T = t;
-  e->C = d.blocks[d.n_blocks - 1].out_channels;
+  return CHIRON_OK;
+}
 
-  // ---- LSTM layers.  z column n of a direction: gate = n / H, unit = n % H (the order of the TF kernel's columns).
+// One LSTM layer from the TF kernels kern[dir] [in_w + H][4H] and biases bias[dir] [4H]: the x-projection GEMMs and W_hh in the
+// operand order of every recurrence kernel the dtype can run.  z column n of a direction: gate = n / H, unit = n % H (the order
+// of the TF kernel's columns).
+static chiron_status plan_lstm_layer(chiron_engine* e, int l, const float* const kern[2], const float* const bias[2]) {
+  const chiron_model_desc& d = e->desc;
   const int H = d.hidden;
   const int zc = 4 * H;
-  for (int l = 0; l < d.rnn_layers; ++l) {
-    LstmPlan lp;
-    lp.in_w = lstm_in_width(&d, l);
-    const float* kern[2];
-    const float* bias[2];
-    for (int dir = 0; dir < 2; ++dir) {
-      kern[dir] = p;
-      e->lstm_kernel_off[dir].push_back((size_t)(p - w));
-      p += (size_t)(lp.in_w + H) * 4 * H;
-      bias[dir] = p;
-      p += 4 * H;
+  LstmPlan lp;
+  lp.in_w = e->map.lstm_in[l];
+  // kern[dir][k_off + k][g * H + unit], 0 outside the width x H matrix that starts at row k_off; W_hh is the H rows below W_x's in_w
+  auto wat = [&](int dir, int k_off, int width, int k, int g, int unit) -> float {
+    return k < width && unit < H ? kern[dir][(size_t)(k_off + k) * 4 * H + g * H + unit] : 0.f;
+  };
+  auto whh = [&](int dir, int k, int g, int unit) -> float { return wat(dir, lp.in_w, H, k, g, unit); };
+  const bool split = d.rnn_kind == CHIRON_RNN_MULTI && l > 0;
+  lp.nproj = split ? 2 : 1;
+  const int Kp = roundup(lp.in_w, e->kq);
+  chiron_status st;
+  for (int pj = 0; pj < lp.nproj; ++pj) {
+    const int ndir = split ? 1 : 2;
+    const int N = ndir * zc;
+    const int Npad = std::max(roundup(N, GEMM_BN), roundup(N, 160));  // the DMA kernel reads whole 160-row weight tiles
+    std::vector<float> Wt((size_t)Npad * Kp, 0.f), sh(Npad, 0.f);
+    for (int n = 0; n < N; ++n) {
+      const int dir = split ? pj : n / zc;
+      const int nl = n % zc;
+      const int g = nl / H, unit = nl % H;
+      for (int k = 0; k < lp.in_w; ++k) Wt[(size_t)n * Kp + k] = kern[dir][(size_t)k * 4 * H + g * H + unit];
+      // forget_bias = 1.0 (TF LSTMCell default; Add(+1.0) const in the .meta while-body) folded here
+      sh[n] = bias[dir][g * H + unit] + (g == 2 ? 1.0f : 0.0f);
     }
-    const bool split = d.rnn_kind == CHIRON_RNN_MULTI && l > 0;
-    lp.nproj = split ? 2 : 1;
-    const int Kp = roundup(lp.in_w, e->kq);
-    chiron_status st;
-    for (int pj = 0; pj < lp.nproj; ++pj) {
-      const int ndir = split ? 1 : 2;
-      const int N = ndir * zc;
-      const int Npad = std::max(roundup(N, GEMM_BN), roundup(N, 160));  // the DMA kernel reads whole 160-row weight tiles
-      std::vector<float> Wt((size_t)Npad * Kp, 0.f), sh(Npad, 0.f);
-      for (int n = 0; n < N; ++n) {
-        const int dir = split ? pj : n / zc;
-        const int nl = n % zc;
-        const int g = nl / H, unit = nl % H;
-        for (int k = 0; k < lp.in_w; ++k) Wt[(size_t)n * Kp + k] = kern[dir][(size_t)k * 4 * H + g * H + unit];
-        // forget_bias = 1.0 (TF LSTMCell default; Add(+1.0) const in the .meta while-body) folded here
-        sh[n] = bias[dir][g * H + unit] + (g == 2 ? 1.0f : 0.0f);
-      }
-      if ((st = upload_gemm(e, &lp.proj[pj], Wt, sh, N, Npad, Kp))) return st;
-    }
-    // recurrent weights in MFMA B-operand order: [dir][wave][k][lane], lane = gate*16 + (unit & 15)
-    std::vector<float> wf((size_t)2 * LSTM_NW * LSTM_K * 64, 0.f);
+    if ((st = upload_gemm(e, &lp.proj[pj], Wt, sh, N, Npad, Kp))) return st;
+  }
+  // recurrent weights in MFMA B-operand order: [dir][wave][k][lane], lane = gate*16 + (unit & 15)
+  std::vector<float> wf((size_t)2 * LSTM_NW * LSTM_K * 64, 0.f);
+  for (int dir = 0; dir < 2; ++dir)
+    for (int wv = 0; wv < LSTM_NW; ++wv)
+      for (int k = 0; k < LSTM_K; ++k)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int g = lane >> 4, unit = 16 * wv + (lane & 15);
+          wf[(((size_t)dir * LSTM_NW + wv) * LSTM_K + k) * 64 + lane] = whh(dir, k, g, unit);
+        }
+  if (e->f16) {
+    // v_mfma_f32_4x4x4_16B_f16 B-operand order: [dir][wave][k-step j][lane][4 halves], k = 4j .. 4j+3
+    std::vector<_Float16> wh((size_t)2 * LSTM_NW * LSTM_KSTEPS16 * 64 * 4, (_Float16)0.f);
     for (int dir = 0; dir < 2; ++dir)
       for (int wv = 0; wv < LSTM_NW; ++wv)
-        for (int k = 0; k < LSTM_K; ++k)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int g = lane >> 4, unit = 16 * wv + (lane & 15);
-            float v = 0.f;
-            if (k < H && unit < H) v = kern[dir][(size_t)(lp.in_w + k) * 4 * H + g * H + unit];
-            wf[(((size_t)dir * LSTM_NW + wv) * LSTM_K + k) * 64 + lane] = v;
-          }
-    if (e->f16) {
-      // v_mfma_f32_4x4x4_16B_f16 B-operand order: [dir][wave][k-step j][lane][4 halves], k = 4j .. 4j+3
-      std::vector<_Float16> wh((size_t)2 * LSTM_NW * LSTM_KSTEPS16 * 64 * 4, (_Float16)0.f);
-      for (int dir = 0; dir < 2; ++dir)
-        for (int wv = 0; wv < LSTM_NW; ++wv)
-          for (int j = 0; j < LSTM_KSTEPS16; ++j)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int q = 0; q < 4; ++q) {
-                const int k = 4 * j + q, g = lane >> 4, unit = 16 * wv + (lane & 15);
-                if (k < H && unit < H)
-                  wh[((((size_t)dir * LSTM_NW + wv) * LSTM_KSTEPS16 + j) * 64 + lane) * 4 + q] =
-                      (_Float16)kern[dir][(size_t)(lp.in_w + k) * 4 * H + g * H + unit];
-              }
-      _Float16* d16 = nullptr;
-      if ((st = dev_upload(e, &d16, wh))) return st;
-      lp.wfrag = reinterpret_cast<float*>(d16);
-      if (H == 100) {
-        // lstm16w_kernel: [dir][wave 8][slot 4][k-step 7][lane][4 halves]; lane = kq*16 + 4u + gate, tile = 3 wave + slot
-        std::vector<_Float16> ww((size_t)2 * 8 * 4 * 7 * 64 * 4, (_Float16)0.f);
-        for (int dir = 0; dir < 2; ++dir)
-          for (int wv = 0; wv < 8; ++wv)
-            for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
-              for (int ks = 0; ks < 7; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                  for (int q = 0; q < 4; ++q) {
-                    const int k = 16 * ks + 4 * (lane >> 4) + q, g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
-                    if (k < H && unit < H)
-                      ww[(((((size_t)dir * 8 + wv) * 4 + slot) * 7 + ks) * 64 + lane) * 4 + q] =
-                          (_Float16)kern[dir][(size_t)(lp.in_w + k) * 4 * H + g * H + unit];
-                  }
-        _Float16* dw = nullptr;
-        if ((st = dev_upload(e, &dw, ww))) return st;
-        lp.wwide = dw;
-        if (lp.nproj == 1 && (lp.in_w == 256 || lp.in_w == 200)) {
-          // lstm16f_kernel (v_mfma_f32_16x16x32_f16): W_x and W_hh as [dir][wave][slot][k-step of 32][lane][8 halves],
-          // lane = kg*16 + 4u + gate -> k = 32 ks + 8 kg + e, column gate*H + 4 (3 wave + slot) + u; zero past the width
-          const int ksx = lp.in_w == 256 ? 8 : 7;
-          auto frag = [&](int ksteps, int k_off, int width) {
-            std::vector<_Float16> v((size_t)2 * 8 * 4 * ksteps * 64 * 8, (_Float16)0.f);
-            for (int dir = 0; dir < 2; ++dir)
-              for (int wv = 0; wv < 8; ++wv)
-                for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
-                  for (int ks = 0; ks < ksteps; ++ks)
-                    for (int lane = 0; lane < 64; ++lane)
-                      for (int q = 0; q < 8; ++q) {
-                        const int k = 32 * ks + 8 * (lane >> 4) + q, g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
-                        if (k < width && unit < H)
-                          v[(((((size_t)dir * 8 + wv) * 4 + slot) * ksteps + ks) * 64 + lane) * 8 + q] =
-                              (_Float16)kern[dir][(size_t)(k_off + k) * 4 * H + g * H + unit];
-                      }
-            return v;
-          };
-          _Float16 *dx = nullptr, *dh = nullptr;
-          if ((st = dev_upload(e, &dx, frag(ksx, 0, lp.in_w)))) return st;
-          if ((st = dev_upload(e, &dh, frag(4, lp.in_w, H)))) return st;
-          lp.wxwide = dx;
-          lp.whfused = dh;
-          lp.wx_ksteps = ksx;
-        }
-      }
-    } else if ((st = dev_upload(e, &lp.wfrag, wf))) {
-      return st;
-    }
-    if (e->w2 && H != 100) return fail(CHIRON_ERR_INVALID, "dtype f16-w2: the recurrence kernel is built for hidden=100");
-    if ((e->w2 || (e->split && getenv("CHIRON_SPLIT_REC32") == nullptr)) && H == 100) {
-      // lstm32s_kernel: [hi | lo][dir][wave 8][slot 4][k-step 7][lane][4 halves]; lane = kq*16 + 4u + gate, tile = 3 wave + slot (the order
-      // of lstm16w_kernel's fragments), every weight as an exact hi + lo half pair
-      const size_t half = (size_t)2 * 8 * 4 * 7 * 64 * 4;
-      std::vector<_Float16> ws(2 * half, (_Float16)0.f);
+        for (int j = 0; j < LSTM_KSTEPS16; ++j)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int q = 0; q < 4; ++q) {
+              const int k = 4 * j + q, g = lane >> 4, unit = 16 * wv + (lane & 15);
+              wh[((((size_t)dir * LSTM_NW + wv) * LSTM_KSTEPS16 + j) * 64 + lane) * 4 + q] = (_Float16)whh(dir, k, g, unit);
+            }
+    _Float16* d16 = nullptr;
+    if ((st = dev_upload(e, &d16, wh))) return st;
+    lp.wfrag = reinterpret_cast<float*>(d16);
+    if (H == 100) {
+      // lstm16w_kernel: [dir][wave 8][slot 4][k-step 7][lane][4 halves]; lane = kq*16 + 4u + gate, tile = 3 wave + slot
+      std::vector<_Float16> ww((size_t)2 * 8 * 4 * 7 * 64 * 4, (_Float16)0.f);
       for (int dir = 0; dir < 2; ++dir)
         for (int wv = 0; wv < 8; ++wv)
           for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
@@ -798,62 +677,118 @@ static chiron_status build_plans(chiron_engine* e, const float* w) {
               for (int lane = 0; lane < 64; ++lane)
                 for (int q = 0; q < 4; ++q) {
                   const int k = 16 * ks + 4 * (lane >> 4) + q, g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
-                  if (k < H && unit < H) {
-                    const float wv32 = kern[dir][(size_t)(lp.in_w + k) * 4 * H + g * H + unit];
-                    const _Float16 hi = (_Float16)wv32;
-                    const size_t at = (((((size_t)dir * 8 + wv) * 4 + slot) * 7 + ks) * 64 + lane) * 4 + q;
-                    ws[at] = hi;
-                    ws[half + at] = (_Float16)(wv32 - (float)hi);
-                  }
+                  ww[(((((size_t)dir * 8 + wv) * 4 + slot) * 7 + ks) * 64 + lane) * 4 + q] = (_Float16)whh(dir, k, g, unit);
                 }
-      _Float16* dws = nullptr;
-      if ((st = dev_upload(e, &dws, ws))) return st;
-      lp.wsplit = dws;
-    }
-    if (!e->f16) {
-      // light-wave fragment of lstm_pair_kernel: [dir][m = 4q + a][lane = kg*16 + gate*4 + j] = W_hh[16q + 4kg + a][gate*H + 96 + j]
-      std::vector<float> wl((size_t)2 * 28 * 64, 0.f);
-      for (int dir = 0; dir < 2; ++dir)
-        for (int m = 0; m < 28; ++m)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int q = m >> 2, a = m & 3, kg = lane >> 4, g = (lane >> 2) & 3, j = lane & 3;
-            const int k = 16 * q + 4 * kg + a;
-            if (k < H) wl[((size_t)dir * 28 + m) * 64 + lane] = kern[dir][(size_t)(lp.in_w + k) * 4 * H + g * H + 96 + j];
-          }
-      if ((st = dev_upload(e, &lp.wlight, wl))) return st;
-      if (H == 100) {
-        // lstm32w_kernel: [dir][wave 8][slot 4][k-step 25][lane]; lane = kq*16 + 4u + gate, tile = 3 wave + slot
-        std::vector<float> ww((size_t)2 * 8 * 4 * 25 * 64, 0.f);
-        for (int dir = 0; dir < 2; ++dir)
-          for (int wv = 0; wv < 8; ++wv)
-            for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
-              for (int ks = 0; ks < 25; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                  const int k = 4 * ks + (lane >> 4), g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
-                  ww[((((size_t)dir * 8 + wv) * 4 + slot) * 25 + ks) * 64 + lane] = kern[dir][(size_t)(lp.in_w + k) * 4 * H + g * H + unit];
-                }
-        if ((st = dev_upload(e, &lp.wwide32, ww))) return st;
+      _Float16* dw = nullptr;
+      if ((st = dev_upload(e, &dw, ww))) return st;
+      lp.wwide = dw;
+      if (lp.nproj == 1 && (lp.in_w == 256 || lp.in_w == 200)) {
+        // lstm16f_kernel (v_mfma_f32_16x16x32_f16): W_x and W_hh as [dir][wave][slot][k-step of 32][lane][8 halves],
+        // lane = kg*16 + 4u + gate -> k = 32 ks + 8 kg + e, column gate*H + 4 (3 wave + slot) + u; zero past the width
+        const int ksx = lp.in_w == 256 ? 8 : 7;
+        auto frag = [&](int ksteps, int k_off, int width) {
+          std::vector<_Float16> v((size_t)2 * 8 * 4 * ksteps * 64 * 8, (_Float16)0.f);
+          for (int dir = 0; dir < 2; ++dir)
+            for (int wv = 0; wv < 8; ++wv)
+              for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
+                for (int ks = 0; ks < ksteps; ++ks)
+                  for (int lane = 0; lane < 64; ++lane)
+                    for (int q = 0; q < 8; ++q) {
+                      const int k = 32 * ks + 8 * (lane >> 4) + q, g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
+                      v[(((((size_t)dir * 8 + wv) * 4 + slot) * ksteps + ks) * 64 + lane) * 8 + q] = (_Float16)wat(dir, k_off, width, k, g, unit);
+                    }
+          return v;
+        };
+        _Float16 *dx = nullptr, *dh = nullptr;
+        if ((st = dev_upload(e, &dx, frag(ksx, 0, lp.in_w)))) return st;
+        if ((st = dev_upload(e, &dh, frag(4, lp.in_w, H)))) return st;
+        lp.wxwide = dx;
+        lp.whfused = dh;
+        lp.wx_ksteps = ksx;
       }
     }
-    e->lstm.push_back(lp);
+  } else if ((st = dev_upload(e, &lp.wfrag, wf))) {
+    return st;
   }
-  // ---- FC head (raw)
-  {
-    chiron_status st;
-    std::vector<float> a(p, p + 2 * H);
-    p += 2 * H;
-    std::vector<float> b(p, p + H);
-    p += H;
-    std::vector<float> c(p, p + (size_t)H * d.classes);
-    p += (size_t)H * d.classes;
-    std::vector<float> dd(p, p + d.classes);
-    p += d.classes;
-    if ((st = dev_upload(e, &e->fc_w, a))) return st;
-    if ((st = dev_upload(e, &e->fc_b, b))) return st;
-    if ((st = dev_upload(e, &e->fc_wc, c))) return st;
-    if ((st = dev_upload(e, &e->fc_bc, dd))) return st;
+  if (e->w2 && H != 100) return fail(CHIRON_ERR_INVALID, "dtype f16-w2: the recurrence kernel is built for hidden=100");
+  if ((e->w2 || (e->split && getenv("CHIRON_SPLIT_REC32") == nullptr)) && H == 100) {
+    // lstm32s_kernel: [hi | lo][dir][wave 8][slot 4][k-step 7][lane][4 halves]; lane = kq*16 + 4u + gate, tile = 3 wave + slot (the order
+    // of lstm16w_kernel's fragments), every weight as an exact hi + lo half pair
+    const size_t half = (size_t)2 * 8 * 4 * 7 * 64 * 4;
+    std::vector<_Float16> ws(2 * half, (_Float16)0.f);
+    for (int dir = 0; dir < 2; ++dir)
+      for (int wv = 0; wv < 8; ++wv)
+        for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
+          for (int ks = 0; ks < 7; ++ks)
+            for (int lane = 0; lane < 64; ++lane)
+              for (int q = 0; q < 4; ++q) {
+                const int k = 16 * ks + 4 * (lane >> 4) + q, g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
+                const float wv32 = whh(dir, k, g, unit);
+                const _Float16 hi = (_Float16)wv32;
+                const size_t at = (((((size_t)dir * 8 + wv) * 4 + slot) * 7 + ks) * 64 + lane) * 4 + q;
+                ws[at] = hi;
+                ws[half + at] = (_Float16)(wv32 - (float)hi);
+              }
+    _Float16* dws = nullptr;
+    if ((st = dev_upload(e, &dws, ws))) return st;
+    lp.wsplit = dws;
   }
+  if (!e->f16) {
+    // light-wave fragment of lstm_pair_kernel: [dir][m = 4q + a][lane = kg*16 + gate*4 + j] = W_hh[16q + 4kg + a][gate*H + 96 + j]
+    std::vector<float> wl((size_t)2 * 28 * 64, 0.f);
+    for (int dir = 0; dir < 2; ++dir)
+      for (int m = 0; m < 28; ++m)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int q = m >> 2, a = m & 3, kg = lane >> 4, g = (lane >> 2) & 3, j = lane & 3;
+          const int k = 16 * q + 4 * kg + a;
+          wl[((size_t)dir * 28 + m) * 64 + lane] = whh(dir, k, g, 96 + j);
+        }
+    if ((st = dev_upload(e, &lp.wlight, wl))) return st;
+    if (H == 100) {
+      // lstm32w_kernel: [dir][wave 8][slot 4][k-step 25][lane]; lane = kq*16 + 4u + gate, tile = 3 wave + slot
+      std::vector<float> ww((size_t)2 * 8 * 4 * 25 * 64, 0.f);
+      for (int dir = 0; dir < 2; ++dir)
+        for (int wv = 0; wv < 8; ++wv)
+          for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
+            for (int ks = 0; ks < 25; ++ks)
+              for (int lane = 0; lane < 64; ++lane) {
+                const int k = 4 * ks + (lane >> 4), g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
+                ww[((((size_t)dir * 8 + wv) * 4 + slot) * 25 + ks) * 64 + lane] = whh(dir, k, g, unit);
+              }
+      if ((st = dev_upload(e, &lp.wwide32, ww))) return st;
+    }
+  }
+  e->lstm.push_back(lp);
   return CHIRON_OK;
+}
+
+// FC head (raw)
+static chiron_status plan_head(chiron_engine* e, const float* w) {
+  const BlobMap& m = e->map;
+  chiron_status st;
+  if ((st = dev_upload(e, &e->fc_w, std::vector<float>(w + m.head_w, w + m.head_b)))) return st;
+  if ((st = dev_upload(e, &e->fc_b, std::vector<float>(w + m.head_b, w + m.head_wc)))) return st;
+  if ((st = dev_upload(e, &e->fc_wc, std::vector<float>(w + m.head_wc, w + m.head_bc)))) return st;
+  return dev_upload(e, &e->fc_bc, std::vector<float>(w + m.head_bc, w + m.total));
+}
+
+static chiron_status build_plans(chiron_engine* e, const float* w) {
+  const chiron_model_desc& d = e->desc;
+  e->bn_batch = d.bn_mode == CHIRON_BN_BATCH;
+  if (e->bn_batch && (e->f16 || e->split)) return fail(CHIRON_ERR_INVALID, "bn_mode=batch is implemented for dtype f32 only");
+  if (e->f16 || e->split) {
+    for (int bi = 0; bi < d.n_blocks; ++bi)
+      if (d.blocks[bi].out_channels % GEMM_BN || (d.blocks[bi].in_channels != 1 && d.blocks[bi].in_channels % 64))
+        return fail(CHIRON_ERR_INVALID, "dtype f16: block %d has %d -> %d channels; the f16 kernels need multiples of 64 / 128", bi,
+                    d.blocks[bi].in_channels, d.blocks[bi].out_channels);
+  }
+  chiron_status st = plan_stem_and_blocks(e, w);
+  for (int l = 0; l < d.rnn_layers && st == CHIRON_OK; ++l) {
+    const float* const kern[2] = {w + e->map.lstm_kernel[l][0], w + e->map.lstm_kernel[l][1]};
+    const float* const bias[2] = {w + e->map.lstm_bias[l][0], w + e->map.lstm_bias[l][1]};
+    st = plan_lstm_layer(e, l, kern, bias);
+  }
+  return st ? st : plan_head(e, w);
 }
 
 // ---- sizes of an engine, computable without a GPU: the frame count, the largest tensor a kernel addresses with a
@@ -864,7 +799,8 @@ static chiron_status build_plans(chiron_engine* e, const float* w) {
 static const uint64_t TENSOR_LIMIT = 0xFFFE0000ull;
 
 static chiron_status plan_sizes(const chiron_model_desc* d, const chiron_engine_opts* o, chiron_engine_sizes* out) {
-  chiron_status st = validate_desc(d);
+  BlobMap map;
+  chiron_status st = blob_map(d, &map);
   if (st) return st;
   if (!o) return fail(CHIRON_ERR_INVALID, "null opts");
   if (o->max_batch < 1 || o->segment_len < 1) return fail(CHIRON_ERR_INVALID, "max_batch/segment_len must be positive");
@@ -873,16 +809,13 @@ static chiron_status plan_sizes(const chiron_model_desc* d, const chiron_engine_
   if (o->max_beam < 0) return fail(CHIRON_ERR_INVALID, "max_beam %d", o->max_beam);
   const bool f16 = o->dtype == CHIRON_F16 || o->dtype == CHIRON_F16_W2, split = o->dtype == CHIRON_F32_SPLIT, bn_batch = d->bn_mode == CHIRON_BN_BATCH;
   const uint64_t B = (uint64_t)o->max_batch, BP = (uint64_t)roundup(o->max_batch, 16), L = (uint64_t)o->segment_len, H = d->hidden, K = d->classes;
-  int t = o->segment_len, left = 0;
+  SiteFrames fr[MAX_SITES];
+  const uint64_t T = (uint64_t)frames(map, o->segment_len, fr);
   uint64_t tmax = 0, cmax = 0;
-  if (d->stem_k > 0) same_pad(t, d->stem_k, d->stem_stride, &t, &left);
-  for (int i = 0; i < d->n_blocks; ++i) {
-    tmax = std::max<uint64_t>(tmax, (uint64_t)t);
-    same_pad(t, d->blocks[i].k, d->blocks[i].stride, &t, &left);
-    tmax = std::max<uint64_t>(tmax, (uint64_t)t);
-    cmax = std::max<uint64_t>(cmax, (uint64_t)d->blocks[i].out_channels);
+  for (int i = map.has_stem; i < map.n_sites; ++i) {   // a block's input and output lengths are among its sites'
+    tmax = std::max<uint64_t>(tmax, (uint64_t)std::max(fr[i].tin, fr[i].tout));
+    cmax = std::max<uint64_t>(cmax, (uint64_t)map.site[i].co);
   }
-  const uint64_t T = (uint64_t)t;
   const uint64_t lasth_ld = !split ? 2 * H : d->rnn_kind == CHIRON_RNN_MULTI ? 2 * (uint64_t)roundup(d->hidden, 32) : (uint64_t)roundup(2 * d->hidden, 32);
   const uint64_t act = B * tmax * cmax * (f16 ? 2 : 4), lasth = T * BP * lasth_ld * 4, z = T * BP * 2 * 4 * H * 4;
   if (B * tmax >= (1ull << 31) || T * BP >= (1ull << 31))
@@ -969,12 +902,11 @@ extern "C" chiron_status chiron_engine_create(const chiron_model_desc* desc, con
                                               const chiron_engine_opts* opts, chiron_engine** out) {
   if (!out) return fail(CHIRON_ERR_INVALID, "null out");
   *out = nullptr;
-  chiron_status st = validate_desc(desc);
+  BlobMap map;
+  chiron_status st = blob_map(desc, &map);
   if (st) return st;
   if (!weights || !opts) return fail(CHIRON_ERR_INVALID, "null weights/opts");
-  size_t want = 0;
-  chiron_weights_size(desc, &want);
-  if (want != n_floats) return fail(CHIRON_ERR_INVALID, "weight blob has %zu floats, descriptor needs %zu", n_floats, want);
+  if (map.total != n_floats) return fail(CHIRON_ERR_INVALID, "weight blob has %zu floats, descriptor needs %zu", n_floats, map.total);
   {
     chiron_engine_sizes sz;
     if ((st = plan_sizes(desc, opts, &sz))) return st;   // argument checks and the 32-bit addressing limits, before any GPU call
@@ -994,6 +926,7 @@ extern "C" chiron_status chiron_engine_create(const chiron_model_desc* desc, con
 
   chiron_engine* e = new chiron_engine();
   e->desc = *desc;
+  e->map = map;
   e->opts = *opts;
   if (e->opts.n_slots < 1) e->opts.n_slots = 1;
   e->L = opts->segment_len;
@@ -2051,7 +1984,7 @@ extern "C" chiron_status chiron_engine_calibrate(chiron_engine* e, const float* 
         const int zc = 4 * H;
         for (int dir = 0; dir < 2; ++dir) {
           if (r.lstm_dir >= 0 && dir != r.lstm_dir) continue;
-          const float* kern = e->host_weights.data() + e->lstm_kernel_off[dir][r.lstm_layer];
+          const float* kern = e->host_weights.data() + e->map.lstm_kernel[r.lstm_layer][dir];
           const int row0 = r.lstm_part == 0 ? 0 : lp.in_w;
           const int nbase = lp.nproj == 1 ? dir * zc : 0;
           for (int col = 0; col < zc; ++col) {

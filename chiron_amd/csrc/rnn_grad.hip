@@ -23,12 +23,11 @@
 //                     (7 waves x one 16-unit tile x 100 k-steps = 100 VGPRs a lane), dc carried in registers.
 //   rg_head_bwd       FC head gradients, per-workgroup partials in row order + the same fixed-order second pass.
 #include "kernels.h"
+#include "model_layout.h"
 
 #include <cstdio>
 
 namespace chiron {
-
-chiron_status set_error(chiron_status st, const char* fmt, ...);   // engine.hip
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -497,8 +496,8 @@ struct RgLayout {
 };
 
 static chiron_status rg_layout(const chiron_model_desc* d, int64_t batch, int64_t T, bool want_shape, RgLayout* o) {
-  size_t total = 0;
-  chiron_status st = chiron_weights_size(d, &total);   // validates the descriptor
+  BlobMap map;
+  chiron_status st = blob_map(d, &map);
   if (st) return st;
   if (d->hidden != RG_H) return set_error(CHIRON_ERR_INVALID, "the training kernels are built for hidden 100, not %d", d->hidden);
   if (d->classes != CHIRON_CLASSES) return set_error(CHIRON_ERR_INVALID, "the training kernels are built for 5 classes, not %d", d->classes);
@@ -508,20 +507,17 @@ static chiron_status rg_layout(const chiron_model_desc* d, int64_t batch, int64_
   L.K = 5;
   L.C = d->blocks[d->n_blocks - 1].out_channels;
   L.multi = d->rnn_kind == CHIRON_RNN_MULTI;
-  size_t n = 0;
+  // the training ABI's params point at the recurrent slice, not at the blob
+  L.first_float = map.cnn_floats;
+  L.n_params = map.total - map.cnn_floats;
   for (int l = 0; l < L.L; ++l) {
-    L.in[l] = l == 0 ? L.C : (L.multi ? RG_H : 2 * RG_H);
+    L.in[l] = map.lstm_in[l];
     for (int dir = 0; dir < 2; ++dir) {
-      L.kernel_off[l][dir] = n;
-      n += (size_t)(L.in[l] + RG_H) * RG_G;
-      L.bias_off[l][dir] = n;
-      n += RG_G;
+      L.kernel_off[l][dir] = map.lstm_kernel[l][dir] - map.cnn_floats;
+      L.bias_off[l][dir] = map.lstm_bias[l][dir] - map.cnn_floats;
     }
   }
-  L.head_off = n;
-  n += RG_HEAD_N;
-  L.n_params = n;
-  L.first_float = total - n;
+  L.head_off = map.head_w - map.cnn_floats;
   if (!want_shape) return CHIRON_OK;
   if (batch < 1 || T < 1) return set_error(CHIRON_ERR_INVALID, "batch %lld, T %lld: both must be positive", (long long)batch, (long long)T);
   if (batch > (1 << 20) || T > CHIRON_CTC_MAX_T) return set_error(CHIRON_ERR_OVERFLOW, "batch %lld / T %lld beyond the training kernels' range (2^20 rows, %d frames)", (long long)batch, (long long)T, CHIRON_CTC_MAX_T);
@@ -552,29 +548,6 @@ static chiron_status rg_layout(const chiron_model_desc* d, int64_t batch, int64_
   const size_t hp = (size_t)L.head_wg * RG_HEAD_N;
   L.part = f; f += part > hp ? part : hp;
   L.ws_floats = f;
-  return CHIRON_OK;
-}
-
-static bool rg_device_ptr(const void* p) {
-  hipPointerAttribute_t a;
-  const bool ok = p && hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeDevice;
-  if (!ok) (void)hipGetLastError();
-  return ok;
-}
-
-static chiron_status rg_enter(const char* who, int32_t device_id) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device_id < 0 || device_id >= ndev) {
-    (void)hipGetLastError();
-    return set_error(CHIRON_ERR_DEVICE, "%s: no HIP device %d: libchiron_amd has no CPU fallback", who, device_id);
-  }
-  if (hipSetDevice(device_id) != hipSuccess) return set_error(CHIRON_ERR_DEVICE, "%s: hipSetDevice(%d) failed", who, device_id);
-  return CHIRON_OK;
-}
-
-static chiron_status rg_launched(const char* who) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(CHIRON_ERR_DEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
   return CHIRON_OK;
 }
 
@@ -611,9 +584,9 @@ extern "C" chiron_status chiron_rnn_train_forward(int32_t device_id, const chiro
   chiron_status st = rg_layout(desc, batch, T, true, &L);
   if (st) return st;
   if (!params || !features || !seq_len || !logits_out || !tape_ || !workspace_) return set_error(CHIRON_ERR_INVALID, "%s: null operand", who);
-  if ((st = rg_enter(who, device_id))) return st;
-  if (!(rg_device_ptr(params) && rg_device_ptr(features) && rg_device_ptr(seq_len) && rg_device_ptr(logits_out) && rg_device_ptr(tape_) &&
-        rg_device_ptr(workspace_)))
+  if ((st = enter_device(who, device_id))) return st;
+  if (!(on_device(params) && on_device(features) && on_device(seq_len) && on_device(logits_out) && on_device(tape_) &&
+        on_device(workspace_)))
     return set_error(CHIRON_ERR_INVALID, "%s: every operand must be device memory on device %d", who, device_id);
   hipStream_t stream = (hipStream_t)stream_;
   float* tape = (float*)tape_;
@@ -667,7 +640,7 @@ extern "C" chiron_status chiron_rnn_train_forward(int32_t device_id, const chiro
   f.H = RG_H;
   f.K = 5;
   launch_fc(f, stream);
-  return rg_launched(who);
+  return launched(who);
 }
 
 extern "C" chiron_status chiron_rnn_train_backward(int32_t device_id, const chiron_model_desc* desc, const float* params, const float* features,
@@ -678,9 +651,9 @@ extern "C" chiron_status chiron_rnn_train_backward(int32_t device_id, const chir
   chiron_status st = rg_layout(desc, batch, T, true, &L);
   if (st) return st;
   if (!params || !features || !seq_len || !dlogits || !tape_ || !workspace_ || !dparams_out) return set_error(CHIRON_ERR_INVALID, "%s: null operand", who);
-  if ((st = rg_enter(who, device_id))) return st;
-  if (!(rg_device_ptr(params) && rg_device_ptr(features) && rg_device_ptr(seq_len) && rg_device_ptr(dlogits) && rg_device_ptr(tape_) &&
-        rg_device_ptr(workspace_) && rg_device_ptr(dparams_out) && (!dfeatures_out || rg_device_ptr(dfeatures_out))))
+  if ((st = enter_device(who, device_id))) return st;
+  if (!(on_device(params) && on_device(features) && on_device(seq_len) && on_device(dlogits) && on_device(tape_) &&
+        on_device(workspace_) && on_device(dparams_out) && (!dfeatures_out || on_device(dfeatures_out))))
     return set_error(CHIRON_ERR_INVALID, "%s: every operand must be device memory on device %d", who, device_id);
   hipStream_t stream = (hipStream_t)stream_;
   const float* tape = (const float*)tape_;
@@ -786,5 +759,5 @@ extern "C" chiron_status chiron_rnn_train_backward(int32_t device_id, const chir
     cur ^= 1;
   }
   if (dfeatures_out) hipLaunchKernelGGL(rg_to_batch_major, dim3(2048), dim3(256), 0, stream, ws + L.dxt, dfeatures_out, L.B, BP, L.T, L.C);
-  return rg_launched(who);
+  return launched(who);
 }

@@ -31,18 +31,12 @@ def _torch():
 
 def params_range(spec):
     """(first float, float count) of the recurrent-plus-head section of the weight blob (chiron_rnn_params_range)."""
-    first, n = C.c_size_t(), C.c_size_t()
-    desc = spec.to_c()
-    _lib.check(_lib.load().chiron_rnn_params_range(C.byref(desc), C.byref(first), C.byref(n)))
-    return int(first.value), int(n.value)
+    return _lib.sized2("chiron_rnn_params_range", C.byref(spec.to_c()))
 
 
 def train_sizes(spec, batch, T):
     """(tape bytes, workspace bytes) of one batch (chiron_rnn_train_sizes).  Host-only."""
-    tape, ws = C.c_size_t(), C.c_size_t()
-    desc = spec.to_c()
-    _lib.check(_lib.load().chiron_rnn_train_sizes(C.byref(desc), int(batch), int(T), C.byref(tape), C.byref(ws)))
-    return int(tape.value), int(ws.value)
+    return _lib.sized2("chiron_rnn_train_sizes", C.byref(spec.to_c()), int(batch), int(T))
 
 
 def param_layout(spec):
@@ -356,18 +350,12 @@ BN_DECAY = 0.99   # cnn.py:125 batchnorm(decay=0.99)
 
 def cnn_params_range(spec):
     """(first float, float count) of the CNN section of the weight blob (chiron_cnn_params_range)."""
-    first, n = C.c_size_t(), C.c_size_t()
-    desc = spec.to_c()
-    _lib.check(_lib.load().chiron_cnn_params_range(C.byref(desc), C.byref(first), C.byref(n)))
-    return int(first.value), int(n.value)
+    return _lib.sized2("chiron_cnn_params_range", C.byref(spec.to_c()))
 
 
 def cnn_train_sizes(spec, batch, segment_len):
     """(tape bytes, workspace bytes) of one batch (chiron_cnn_train_sizes).  Host-only."""
-    tape, ws = C.c_size_t(), C.c_size_t()
-    desc = spec.to_c()
-    _lib.check(_lib.load().chiron_cnn_train_sizes(C.byref(desc), int(batch), int(segment_len), C.byref(tape), C.byref(ws)))
-    return int(tape.value), int(ws.value)
+    return _lib.sized2("chiron_cnn_train_sizes", C.byref(spec.to_c()), int(batch), int(segment_len))
 
 
 def cnn_param_layout(spec):
