@@ -507,9 +507,14 @@ struct CgLayout {
   size_t buf[4], part, sums, ws_floats;   // workspace offsets (floats)
 };
 
-static int cg_nslices(long rows) {
+// the slices of a row reduction: at most CG_MAX_SLICES of `chunk` rows, and no more than hold a row (just past the cap,
+// CG_MAX_SLICES slices of the rounded-up chunk would leave the last ones empty)
+struct CgSlices { int n; long chunk; };
+static CgSlices cg_slices(long rows) {
   long n = (rows + CG_SLICE_ROWS - 1) / CG_SLICE_ROWS;
-  return (int)(n < 1 ? 1 : n > CG_MAX_SLICES ? CG_MAX_SLICES : n);
+  n = n < 1 ? 1 : n > CG_MAX_SLICES ? CG_MAX_SLICES : n;
+  const long chunk = (rows + n - 1) / n;
+  return CgSlices{(int)((rows + chunk - 1) / chunk), chunk};
 }
 static int cg_nsplit(long rows) {
   long n = (rows + CG_DW_SPLIT_ROWS - 1) / CG_DW_SPLIT_ROWS;
@@ -561,9 +566,9 @@ static chiron_status cg_layout(const chiron_model_desc* d, int64_t batch, int64_
   size_t part = 0;
   for (int i = 0; i < ns; ++i) {
     const CgSite& s = L.s[i];
-    size_t p = (size_t)cg_nslices(s.rows) * 2 * s.co;
+    size_t p = (size_t)cg_slices(s.rows).n * 2 * s.co;
     if (p > part) part = p;
-    p = s.ci == 1 ? (size_t)cg_nslices(s.rows) * CG_R1_TAPS * s.co : (size_t)s.k * cg_nsplit(s.rows) * s.ci * s.co;
+    p = s.ci == 1 ? (size_t)cg_slices(s.rows).n * CG_R1_TAPS * s.co : (size_t)s.k * cg_nsplit(s.rows) * s.ci * s.co;
     if (p > part) part = p;
   }
   L.part = f; f += part;
@@ -608,11 +613,12 @@ static void cg_conv_dx(const CgSite& s, const float* dy, const float* w, float* 
 // dw [k][ci][co] = sum over rows of x_tap^T dy
 static void cg_conv_dw(const CgSite& s, const float* x, const float* dy, float* part, float* dw, hipStream_t stream) {
   if (s.ci == 1) {
-    const int nsl = cg_nslices(s.rows);
+    const CgSlices sl = cg_slices(s.rows);
+    const int nsl = sl.n;
     for (int tap0 = 0; tap0 < s.k; tap0 += CG_R1_TAPS) {
       CgRank1 p = {};
       p.x = x; p.dy = dy; p.part = part; p.g = cg_rows_fwd(s); p.k = s.k; p.C = s.co; p.rows = s.rows;
-      p.chunk = (s.rows + nsl - 1) / nsl;
+      p.chunk = sl.chunk;
       p.tap0 = tap0;
       p.nt = s.k - tap0 < CG_R1_TAPS ? s.k - tap0 : CG_R1_TAPS;
       hipLaunchKernelGGL(cg_rank1_dw_kernel, dim3(nsl), dim3(CG_RED_THREADS), 0, stream, p);
@@ -633,8 +639,9 @@ static void cg_conv_dw(const CgSite& s, const float* x, const float* dy, float* 
 
 // the batch's moments of y -> stat, moments_out
 static void cg_moments(const CgSite& s, const float* y, const float* bn, float* stat, float* mom, float* part, hipStream_t stream) {
-  const int nsl = cg_nslices(s.rows);
-  const long chunk = (s.rows + nsl - 1) / nsl;
+  const CgSlices sl = cg_slices(s.rows);
+  const int nsl = sl.n;
+  const long chunk = sl.chunk;
   const unsigned g = (s.co + 255) / 256;
   hipLaunchKernelGGL(cg_sum_kernel, dim3(nsl), dim3(CG_RED_THREADS), 0, stream, y, s.rows, s.co, chunk, (const float*)nullptr, part);
   hipLaunchKernelGGL(cg_mean_finish_kernel, dim3(g), dim3(256), 0, stream, part, nsl, s.co, (float)s.rows, stat);
@@ -645,8 +652,9 @@ static void cg_moments(const CgSite& s, const float* y, const float* bn, float* 
 // ReLU mask + BN backward of one site: din (gradient at the BN / ReLU output) -> dy_out (gradient at the convolution output)
 static void cg_bn_backward(const CgSite& s, const float* din, const float* relu_out, const float* tape, const float* params, float* dparams,
                            float* part, float* sums, float* dy_out, float* g_out, hipStream_t stream) {
-  const int nsl = cg_nslices(s.rows);
-  const long chunk = (s.rows + nsl - 1) / nsl;
+  const CgSlices sl = cg_slices(s.rows);
+  const int nsl = sl.n;
+  const long chunk = sl.chunk;
   const float* stat = tape + s.stat;
   hipLaunchKernelGGL(cg_bn_bwd_sum_kernel, dim3(nsl), dim3(CG_RED_THREADS), 0, stream, din, relu_out, tape + s.y, stat, s.rows, s.co, chunk, part);
   hipLaunchKernelGGL(cg_bn_bwd_finish_kernel, dim3((s.co + 255) / 256), dim3(256), 0, stream, part, nsl, s.co, sums, dparams + s.bn_off);

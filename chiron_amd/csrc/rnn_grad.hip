@@ -56,6 +56,7 @@ struct RgGemm {
 };
 
 constexpr int GT = 128, GK = 16, GLD = GT + 4;
+constexpr int RG_MAX_GRID_Y = 65535;   // a grid's y extent: HIP documents 65535, the MI355X reports 65536
 
 __global__ __launch_bounds__(256) void rg_gemm_kernel(const RgGemm p) {
   __shared__ float As[GK][GLD];
@@ -523,6 +524,10 @@ static chiron_status rg_layout(const chiron_model_desc* d, int64_t batch, int64_
   if (batch > (1 << 20) || T > CHIRON_CTC_MAX_T) return set_error(CHIRON_ERR_OVERFLOW, "batch %lld / T %lld beyond the training kernels' range (2^20 rows, %d frames)", (long long)batch, (long long)T, CHIRON_CTC_MAX_T);
   const int64_t BP = (batch + RG_ROWS - 1) / RG_ROWS * RG_ROWS;
   if (BP * T > (1 << 24)) return set_error(CHIRON_ERR_OVERFLOW, "T * padded batch = %lld rows: the training kernels index at most 2^24", (long long)(BP * T));
+  // the x-projection and dX GEMMs put their T * BP / GT row tiles on grid.y (the tighter of the two bounds as the constants stand)
+  if (BP * T > (int64_t)GT * RG_MAX_GRID_Y)
+    return set_error(CHIRON_ERR_OVERFLOW, "T * padded batch = %lld rows: the training GEMMs launch at most %d row tiles of %d rows (%lld rows)",
+                     (long long)(BP * T), RG_MAX_GRID_Y, GT, (long long)GT * RG_MAX_GRID_Y);
   L.B = (int)batch;
   L.BP = (int)BP;
   L.T = (int)T;

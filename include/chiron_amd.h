@@ -457,8 +457,9 @@ chiron_status chiron_rnn_params_range(const chiron_model_desc* desc, size_t* fir
  * step, row and direction the four activated gates and the cell state) and of the workspace (x-projections, gate derivatives,
  * dh buffers, split-K partial sums) for one batch of `batch` windows of T frames.  Both grow linearly in the batch rounded up to
  * 16 rows.  Host-only (no GPU needed).  CHIRON_ERR_INVALID: batch < 1, T < 1, unsupported topology.  CHIRON_ERR_OVERFLOW: T >
- * CHIRON_CTC_MAX_T, batch > 2^20, or T * roundup(batch, 16) > 2^24 rows; within those bounds every offset the kernels form is
- * 64-bit.  The launchers below make the same checks.                                                                              */
+ * CHIRON_CTC_MAX_T, batch > 2^20, or T * roundup(batch, 16) > 128 * 65535 = 8 388 480 rows (the GEMMs' 128-row tiles lie along a
+ * grid's y extent, and the kernels index at most 2^24 rows); within those bounds every offset the kernels form is 64-bit.  The
+ * launchers below make the same checks.                                                                                           */
 chiron_status chiron_rnn_train_sizes(const chiron_model_desc* desc, int32_t batch, int32_t T, size_t* tape_bytes, size_t* workspace_bytes);
 
 /* Forward with a tape (rnn.py:20-174 + :72-96 in training): logits_out [batch, T, 5] from features [batch, T, C] (the tensor of

@@ -147,3 +147,36 @@ def grad_case(kind, B, L):
     rng = np.random.default_rng(1000 * B + L)
     g = rng.normal(size=(B, spec.output_len(L), spec.blocks[-1]["out"])).astype(np.float32)
     return spec, w, x, g
+
+
+# Past the caps of the row reductions of csrc/cnn_grad.hip (CG_MAX_SLICES slices of CG_SLICE_ROWS rows, CG_DW_MAX_SPLIT dW splits of
+# CG_DW_SPLIT_ROWS rows: both 131 072 rows), seeded by grad_case like the cases above; tests/test_cnn_train_cpu.py pins them to the
+# constants.  The smallest shapes that cross each cap with a ragged last slice:
+#   rna B 300 L 500  the trainer's default batch: conv2a of block 1 reads the signal (ci == 1) at 150 000 rows, 512 slices of 293 rows
+#                    (the last 277) in cg_sum_kernel, cg_bn_bwd_sum_kernel and cg_rank1_dw_kernel; the stride-5 sites have 30 000 rows
+#   dna B 330 L 400  every site has 132 000 rows: 512 slices of 258 rows (the last 162), 64 dW splits of 2064 rows (the last 1968)
+CAP_GRAD_CASES = [("rna", 300, 500), ("dna", 330, 400)]
+# the factors of the bar for these cases: max(4, 1.5 x the largest max / median) of the float32 ensemble over them, run on the CPU before
+# any HIP result (tools/cnn_grad_accuracy.py -> "factor_cap" of profiles/cnn_grad_accuracy.json; tests/test_cnn_train_cpu.py compares)
+CAP_FWD_FACTOR = 4.0
+CAP_GRAD_FACTOR = 4.4321
+
+
+def site_rows(spec, B, L):
+    """[(site, ci, k, rows)]: the rows = B * output frames of every convolution site, the 'SAME' walk of csrc/model_layout.h restated:
+    both branches of a block read the block's input, branch1 and conv2b carry its stride, conv2c runs at its output length."""
+    out, t = [], L
+    for site, (_, k, ci, _), _ in spec._sites():
+        leaf = site.split("/")[-1]
+        if leaf == "conv2a":
+            out.append((site, ci, k, B * t))
+            continue
+        if leaf == "conv2c":
+            out.append((site, ci, k, B * t))
+            continue
+        stride = spec.stem["stride"] if site == spec.STEM_SITE else next(b["stride"] for b in spec.blocks if site.startswith(b["name"] + "/"))
+        tout = -(-t // stride)
+        out.append((site, ci, k, B * tout))
+        if leaf != "conv1" or site == spec.STEM_SITE:      # the stem and conv2b hand their output length on; branch1 (conv1) does not
+            t = tout
+    return out

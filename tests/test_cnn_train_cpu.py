@@ -1,7 +1,9 @@
 """CPU tests of the CNN training seam: the float64 reference against the oracle, the host-only ABI queries, init_weights, the
 batch-BN checkpoint writer and the `train` command line."""
 import ctypes as C
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -11,6 +13,7 @@ from chiron_amd import _lib, entry, tf_bundle, train
 
 import cnn_ref
 import cnn_train_cases as cc
+import train_cases as tc
 
 
 @pytest.mark.parametrize("kind", cc.SPECS)
@@ -82,6 +85,91 @@ def test_cnn_train_sizes_refuse_bad_and_oversized_shapes(built):
     a, b = C.c_size_t(), C.c_size_t()
     assert _lib.load().chiron_cnn_train_sizes(C.byref(bad), 16, 400, C.byref(a), C.byref(b)) == _lib.ERR_INVALID
     assert _lib.load().chiron_cnn_params_range(C.byref(bad), C.byref(a), C.byref(b)) == _lib.ERR_INVALID
+
+
+# ---------------------------------------------------------------------------------------------
+# the cases past the reduction caps against the kernels' own constants
+# ---------------------------------------------------------------------------------------------
+class _CgGeometry:
+    """csrc/cnn_grad.hip's slicing of a site's rows, restated: cg_slices with its unrounded chunk (cg_sum_kernel,
+    cg_bn_bwd_sum_kernel, cg_rank1_dw_kernel) and cg_nsplit with cg_dw_kernel's chunk, rounded up to the k-tile."""
+    def __init__(self):
+        k = tc.kernel_constants("cnn_grad.hip", ["CG_SLICE_ROWS", "CG_MAX_SLICES", "CG_DW_SPLIT_ROWS", "CG_DW_MAX_SPLIT", "CK"])
+        self.slice_rows, self.max_slices, self.split_rows, self.max_split, self.ck = (
+            k["CG_SLICE_ROWS"], k["CG_MAX_SLICES"], k["CG_DW_SPLIT_ROWS"], k["CG_DW_MAX_SPLIT"], k["CK"])
+
+    def slice_chunk(self, rows):
+        return -(-rows // min(max(-(-rows // self.slice_rows), 1), self.max_slices))
+
+    def nslices(self, rows):
+        return -(-rows // self.slice_chunk(rows))
+
+    def nsplit(self, rows):
+        return min(max(-(-rows // self.split_rows), 1), self.max_split)
+
+    def dw_chunk(self, rows):
+        return -(-(-(-rows // self.nsplit(rows))) // self.ck) * self.ck
+
+
+def _ragged_last(rows, n, chunk):
+    tc.assert_slices_tile(rows, n, chunk)
+    last = tc.slices(rows, n, chunk)[-1]
+    assert 0 < last[1] - last[0] < chunk
+    return last[1] - last[0]
+
+
+def test_cap_cases_lie_past_the_caps_of_the_kernels_constants():
+    """CAP_GRAD_CASES exist to run the row reductions of csrc/cnn_grad.hip where their slice counts are capped; a change of a constant
+    there must not put them back below the caps unnoticed."""
+    g = _CgGeometry()
+    sites = {(kind, B, L): cc.site_rows(cc.spec_of(kind), B, L) for kind, B, L in cc.CAP_GRAD_CASES}
+    for case, rows_of in sites.items():
+        assert rows_of[-1][3] == case[1] * cc.spec_of(case[0]).output_len(case[2])      # the walk ends at the features' frames
+        for _, _, _, rows in rows_of:
+            tc.assert_slices_tile(rows, g.nslices(rows), g.slice_chunk(rows))
+            tc.assert_slices_tile(rows, g.nsplit(rows), g.dw_chunk(rows))
+    # rna at the trainer's default batch: the site that reads the signal at full length is past the slice cap, the rest below both
+    rna = sites[("rna", 300, 500)]
+    past = [(site, ci, k, rows) for site, ci, k, rows in rna if rows > g.slice_rows * g.max_slices]
+    assert [(ci, rows) for _, ci, _, rows in past] == [(1, 150000)]
+    assert g.nslices(150000) == g.max_slices < -(-150000 // g.slice_rows)
+    assert (g.slice_chunk(150000), _ragged_last(150000, g.max_slices, g.slice_chunk(150000))) == (293, 277)
+    assert all(rows == 30000 for _, _, _, rows in rna if rows != 150000)
+    # dna: every site is past both caps
+    dna = sites[("dna", 330, 400)]
+    assert all(rows == 132000 for _, _, _, rows in dna) and any(ci == 1 for _, ci, _, _ in dna) and any(k > 1 for _, _, k, _ in dna)
+    assert g.nslices(132000) == g.max_slices < -(-132000 // g.slice_rows)
+    assert g.nsplit(132000) == g.max_split < -(-132000 // g.split_rows)
+    assert (g.slice_chunk(132000), _ragged_last(132000, g.max_slices, g.slice_chunk(132000))) == (258, 162)
+    assert (g.dw_chunk(132000), _ragged_last(132000, g.max_split, g.dw_chunk(132000))) == (2064, 1968)
+
+
+def test_row_slices_tile_every_row_count():
+    """No slice of a row reduction or of cg_dw_kernel's split is empty, and the slices tile [0, rows).  (Just past the cap, as at
+    131 073 rows, CG_MAX_SLICES slices of the rounded-up chunk would leave the last ones empty: cg_slices launches only those that
+    hold a row.)"""
+    g = _CgGeometry()
+    rng = np.random.default_rng(6)
+    cap = g.slice_rows * g.max_slices
+    edge = [1, 2, g.slice_rows, g.slice_rows + 1, g.split_rows, g.split_rows + 1, cap - 1, cap, cap + 1, g.split_rows * g.max_split + 1,
+            (1 << 24) - 1, 1 << 24]
+    some = np.concatenate([rng.integers(1, 1 << 12, 1000), rng.integers(1, 1 << 18, 2000), rng.integers(1, (1 << 24) + 1, 2000)])
+    for rows in edge + [int(v) for v in some]:
+        tc.assert_slices_tile(rows, g.nslices(rows), g.slice_chunk(rows))
+        tc.assert_slices_tile(rows, g.nsplit(rows), g.dw_chunk(rows))
+
+
+def test_cap_factors_are_the_ensemble_tools():
+    """The factors the GPU test holds the cap cases to are what tools/cnn_grad_accuracy.py derived on the CPU: max(4, 1.5 x the
+    largest max / median of the float32 ensemble over exactly these cases)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prof = json.load(open(os.path.join(root, "profiles", "cnn_grad_accuracy.json")))
+    assert sorted(prof["cap"]["cases"]) == sorted("%s B%d L%d" % c for c in cc.CAP_GRAD_CASES)
+    for part, factor in (("forward", cc.CAP_FWD_FACTOR), ("gradients", cc.CAP_GRAD_FACTOR)):
+        largest = max(r["max_over_median"] for case in prof["cap"]["cases"].values() for r in case[part].values())
+        assert prof["cap"]["largest_max_over_median"][part] == largest
+        assert prof["factor_cap"][part] == max(4.0, 1.5 * largest)
+        assert abs(factor - prof["factor_cap"][part]) <= 5e-5 and factor >= 4.0, (part, factor, prof["factor_cap"][part])
 
 
 @pytest.mark.parametrize("bn_mode", ["population", "batch"])

@@ -124,6 +124,25 @@ def test_gradients_against_float64_autograd(built, case, source):
     cc.assert_rows(rows, label, GRAD_FACTOR)
 
 
+@pytest.mark.parametrize("case", cc.CAP_GRAD_CASES, ids=lambda c: "%s-B%d-L%d" % c)
+def test_gradients_past_the_reduction_caps(built, case):
+    """Sites of more than 131 072 rows (cnn_train_cases.CAP_GRAD_CASES): the row reductions run 512 capped slices and cg_dw_kernel 64
+    capped splits, each with a ragged last one.  The forward (features, every site's moments) and every gradient are held to the bar
+    of the cases above, with the factors the same ensemble rule gave for these two cases on the CPU before any HIP result
+    (profiles/cnn_grad_accuracy.json, "factor_cap": forward 4, gradients 4.4321 from a largest ratio of 2.955 at dna B 330)."""
+    kind, B, L = case
+    spec, w, x, g = cc.grad_case(kind, B, L)
+    fea, mom, dp, g_used, masks = cc.hip_run(spec, w, x, g)
+    label = "%s B=%d L=%d" % (kind, B, L)
+    cc.assert_rows(cc.forward_rows(spec, w, x, fea, mom, cc.CAP_FWD_FACTOR), label + " fwd", cc.CAP_FWD_FACTOR)
+    rows = cc.gradient_rows(spec, w, x, dp, g_used, masks, cc.CAP_GRAD_FACTOR, label)
+    assert set(rows) == set(cnn_ref.trainable_names(spec))
+    cc.assert_rows(rows, label, cc.CAP_GRAD_FACTOR)
+    # the slices are summed in slice order: two identical calls, the same bits
+    fea2, mom2, dp2, _ = cc.hip_forward_backward(spec, w, x, g)
+    assert fea2.tobytes() == fea.tobytes() and mom2.tobytes() == mom.tobytes() and dp2.tobytes() == dp.tobytes()
+
+
 # ---------------------------------------------------------------------------------------------
 # exact properties
 # ---------------------------------------------------------------------------------------------

@@ -83,6 +83,20 @@ def test_gradients_against_float64_autograd(built, kind, T, source):
     _assert_rows(tc.accuracy(spec, w, fea, sl, dl), "%s T=%d %s" % (kind, T, source))
 
 
+@pytest.mark.parametrize("case", tc.CAP_CASES, ids=lambda c: "%s-B%d-T%d-%s" % c)
+def test_gradients_past_the_reduction_caps(built, case):
+    """More rows than the caps of the reductions over T * BP rows provide for (tests/train_cases.py, CAP_CASES): the head backward's
+    workgroups straddle frames and padding rows, the split-K GEMMs and the column sum run 64 capped slices with a ragged last one.
+    Every tensor is held to the bar of the cases above."""
+    kind, B, T, what = case
+    spec, w, fea, sl, dl = tc.cap_case(kind, B, T)
+    hip = {}
+    _assert_rows(tc.accuracy(spec, w, fea, sl, dl, hip_out=hip), "%s B=%d T=%d %s" % case)
+    if what == "split":     # the slices are summed in slice order: two identical calls, the same bits
+        _, _, dfeat2, flat2, _ = tc.hip_forward_backward(spec, w, fea, sl, dl)
+        assert flat2.tobytes() == hip["flat"].tobytes() and dfeat2.tobytes() == hip["dfeatures"].tobytes()
+
+
 @pytest.mark.parametrize("name", ["write-through", "closed", "integrate-no-output", "hold-and-output", "midpoint"])
 def test_gradients_with_saturated_gates(built, name):
     spec = ca.dna_default_spec()

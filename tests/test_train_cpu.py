@@ -10,6 +10,7 @@ import chiron_amd as ca
 from chiron_amd import _lib, entry, tf_bundle, train
 
 import rnn_ref
+import train_cases as tc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -72,12 +73,92 @@ def test_train_sizes_refuse_bad_shapes(built):
     assert _sizes_status(spec, 16, 8193) == _lib.ERR_OVERFLOW          # T > CHIRON_CTC_MAX_T
     assert _sizes_status(spec, 1 << 19, 400) == _lib.ERR_OVERFLOW      # T * batch > 2^24 rows
     assert _sizes_status(spec, (1 << 20) + 1, 1) == _lib.ERR_OVERFLOW
+    # the GEMMs over the T * BP rows put their 128-row tiles on a grid's y extent: at most 65535 of them
+    assert 255 * 32896 == 128 * 65535 and 32896 % 16 == 0
+    assert _sizes_status(spec, 32896, 255) == _lib.OK
+    assert _sizes_status(spec, 32897, 255) == _lib.ERR_OVERFLOW        # 255 * 32912 rows, still below 2^24
+    assert b"row tiles" in _lib.load().chiron_last_error()
     small = ca.dna_default_spec()
     small.hidden = 64
     assert _sizes_status(small, 16, 400) == _lib.ERR_INVALID           # the kernels are built for hidden 100
     desc = small.to_c()
     a, b = C.c_size_t(), C.c_size_t()
     assert _lib.load().chiron_rnn_params_range(C.byref(desc), C.byref(a), C.byref(b)) == _lib.ERR_INVALID
+
+
+# ---------------------------------------------------------------------------------------------
+# the cases past the reduction caps against the kernels' own constants
+# ---------------------------------------------------------------------------------------------
+class _RgGeometry:
+    """csrc/rnn_grad.hip's slicing of a reduction over rows, restated: rg_nsplit, rg_gemm's chunk (rounded up to the k-tile),
+    the column sum's chunk (not rounded), and rg_layout's head_rows / head_wg."""
+    def __init__(self):
+        k = tc.kernel_constants("rnn_grad.hip", ["RG_SPLIT_ROWS", "RG_MAX_SPLIT", "RG_HEAD_WG", "RG_HEAD_ROWS", "GK"])
+        self.split_rows, self.max_split, self.head_wg_max, self.head_rows_min, self.gk = (
+            k["RG_SPLIT_ROWS"], k["RG_MAX_SPLIT"], k["RG_HEAD_WG"], k["RG_HEAD_ROWS"], k["GK"])
+
+    def nsplit(self, R):
+        return min(max(-(-R // self.split_rows), 1), self.max_split)
+
+    def gemm_chunk(self, R):
+        return -(-(-(-R // self.nsplit(R))) // self.gk) * self.gk
+
+    def colsum_chunk(self, M):
+        return -(-M // self.nsplit(M))
+
+    def head(self, M):
+        rows = max(-(-M // self.head_wg_max), self.head_rows_min)
+        return rows, -(-M // rows)
+
+
+def test_cap_cases_lie_past_the_caps_of_the_kernels_constants():
+    """CAP_CASES exist to run the reductions of csrc/rnn_grad.hip where their slice counts are capped; a change of a constant there
+    must not put them back below the caps unnoticed."""
+    g = _RgGeometry()
+    whats = set()
+    for kind, B, T, what in tc.CAP_CASES:
+        whats.add(what)
+        BP = -(-B // 16) * 16
+        M = T * BP
+        head_rows, head_wg = g.head(M)
+        tc.assert_slices_tile(M, head_wg, head_rows)
+        # the head cap binds: more rows per workgroup than the least, no multiple of the 16-row tiles or of a frame, padding rows present
+        assert M > g.head_wg_max * g.head_rows_min and head_rows > g.head_rows_min and head_wg == g.head_wg_max
+        assert B < BP and head_rows % BP != 0
+        if what == "head":
+            assert head_rows % 16 != 0
+            assert g.nsplit(M) < g.max_split            # the split-K cap is the other cases' business
+            assert (M, head_rows) == (33024, 129)
+        for R in (M, M - BP):                           # dWx and db reduce over M rows, dWh over M - BP
+            tc.assert_slices_tile(R, g.nsplit(R), g.gemm_chunk(R))
+            tc.assert_slices_tile(R, g.nsplit(R), g.colsum_chunk(R))
+        if what == "split":
+            n = g.nsplit(M)
+            assert n == g.max_split and -(-M // g.split_rows) > g.max_split and g.nsplit(M - BP) == g.max_split
+            assert g.gemm_chunk(M) > g.split_rows and g.colsum_chunk(M) > g.split_rows      # the slices grow instead of their count
+            gemm, colsum = tc.slices(M, n, g.gemm_chunk(M)), tc.slices(M, n, g.colsum_chunk(M))
+            assert g.gemm_chunk(M) != g.colsum_chunk(M)                 # the two disagree about the slice borders
+            for sl, chunk in ((gemm, g.gemm_chunk(M)), (colsum, g.colsum_chunk(M)), (tc.slices(M, head_wg, head_rows), head_rows)):
+                assert 0 < sl[-1][1] - sl[-1][0] < chunk                # a ragged last slice
+            assert (M, g.gemm_chunk(M), gemm[-1][1] - gemm[-1][0], g.colsum_chunk(M), head_rows) == (133472, 2096, 1424, 2086, 522)
+            assert (M - BP, g.gemm_chunk(M - BP)) == (132096, 2064) and 64 * 2064 == M - BP     # dWh: the slices fit exactly
+    assert whats == {"head", "split"}
+
+
+def test_row_slices_tile_every_row_count():
+    """For row counts up to 2^24, more than the sizes call admits: no slice of the split-K GEMMs, the column sum or the head backward is
+    empty, and the slices tile [0, rows)."""
+    g = _RgGeometry()
+    rng = np.random.default_rng(5)
+    edge = [1, 2, 15, 16, 17, g.split_rows, g.split_rows + 1, g.split_rows * g.max_split - 1, g.split_rows * g.max_split,
+            g.split_rows * g.max_split + 1, g.head_wg_max * g.head_rows_min, g.head_wg_max * g.head_rows_min + 1, (1 << 24) - 1, 1 << 24]
+    some = np.concatenate([rng.integers(1, 1 << 12, 1000), rng.integers(1, 1 << 18, 2000), rng.integers(1, (1 << 24) + 1, 2000)])
+    for rows in edge + [int(v) for v in some]:
+        tc.assert_slices_tile(rows, g.nsplit(rows), g.gemm_chunk(rows))
+        tc.assert_slices_tile(rows, g.nsplit(rows), g.colsum_chunk(rows))
+        head_rows, head_wg = g.head(rows)
+        tc.assert_slices_tile(rows, head_wg, head_rows)
+        assert head_wg <= g.head_wg_max
 
 
 def test_write_bundle_round_trip_and_crc(built, tmp_path):

@@ -5,6 +5,9 @@ gradients g64; the SAME restatement run in float32 on the CPU gives, per tensor,
 realisation; the HIP gradient must satisfy  ||g - g64|| <= FACTOR * e32 * ||g64|| + 1e-6 * ||g64||,  FACTOR = 4 for the different
 accumulation orders (blocked split-K over T * B rows against torch's order; the repository's ensemble study found float32
 realisations of one formula 2 .. 3 x apart between orders, profiles/r06_parity_dist_*)."""
+import os
+import re
+
 import numpy as np
 import torch
 
@@ -64,10 +67,13 @@ def rel_l2(a, ref):
     return float(np.linalg.norm(np.asarray(a, dtype=np.float64) - ref) / max(np.linalg.norm(ref), 1e-300))
 
 
-def accuracy(spec, weights, fea, seq_len, dlogits):
+def accuracy(spec, weights, fea, seq_len, dlogits, hip_out=None):
     """Per tensor (every named parameter + 'dfeatures'): err (HIP against float64), e32 (float32 restatement against float64),
-    norm of the float64 gradient, and whether the bar holds.  dlogits: array, or callable(logits tensor on the GPU) -> array / tensor."""
-    _, named, dfeat, _, g_used = hip_forward_backward(spec, weights, fea, seq_len, dlogits)
+    norm of the float64 gradient, and whether the bar holds.  dlogits: array, or callable(logits tensor on the GPU) -> array / tensor.
+    hip_out: a dict that receives the HIP run's flat dparams and dfeatures."""
+    _, named, dfeat, flat, g_used = hip_forward_backward(spec, weights, fea, seq_len, dlogits)
+    if hip_out is not None:
+        hip_out.update(flat=flat, dfeatures=dfeat)
     _, g64, dx64 = rnn_ref.gradients(fea, seq_len, spec, weights, g_used, torch.float64)
     _, g32, dx32 = rnn_ref.gradients(fea, seq_len, spec, weights, g_used, torch.float32)
     rows = {}
@@ -82,6 +88,46 @@ def accuracy(spec, weights, fea, seq_len, dlogits):
                       "ratio": err / e32 if e32 > 0 else (0.0 if err == 0 else float("inf")),
                       "ok": bool(err <= FACTOR * e32 + FLOOR * norm)}
     return rows
+
+
+# Past the caps of the reductions over the M = T * BP rows (BP: the batch padded to 16), csrc/rnn_grad.hip; (kind, B, T, what).
+# The smallest shapes that cross each constant with a ragged last slice; tests/test_train_cpu.py pins them to the constants.
+#   "head"   M = 48 * 688 = 33 024 > RG_HEAD_WG * RG_HEAD_ROWS: 256 head workgroups of 129 rows, no multiple of 16, so every
+#            workgroup's range straddles frames and takes in the padding rows 683 .. 687
+#   "split"  M = 97 * 1376 = 133 472 > RG_MAX_SPLIT * RG_SPLIT_ROWS: 64 capped slices; the GEMM's chunk is 2096 (last slice 1424),
+#            the column sum's 2086, dWh's (R = M - BP = 132 096) 2064 exactly; 522 rows per head workgroup
+CAP_CASES = [("dna-stack", 683, 48, "head"), ("rna-multi", 683, 48, "head"), ("dna-stack", 1370, 97, "split")]
+
+
+def cap_case(kind, B, T):
+    """-> (spec, weights, features, seq_len, random dlogits) of one CAP_CASES entry, seeded as test_gradients_against_float64_autograd."""
+    spec = specs()[kind]
+    rng = np.random.default_rng(100 + T)
+    fea = random_features(B, T, 256, rng)
+    sl = ragged_seq_len(B, T, rng)
+    return spec, ca.synthetic_weights(spec, seed=7), fea, sl, rng.normal(size=(B, T, 5)).astype(np.float32)
+
+
+def kernel_constants(hip_file, names):
+    """{name: value} of `constexpr int` constants, read out of chiron_amd/csrc/<hip_file>."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "chiron_amd", "csrc", hip_file)).read()
+    decl = "\n".join(re.findall(r"^constexpr int [^;]*;", src, flags=re.M))
+    out = {}
+    for name in names:
+        found = re.findall(r"\b%s = (\d+)\b" % name, decl)
+        assert len(found) == 1, (hip_file, name, found)
+        out[name] = int(found[0])
+    return out
+
+
+def slices(rows, n, chunk):
+    """[(begin, end)] of the n slices of a row reduction as every kernel forms them: begin = z * chunk, end = min(rows, begin + chunk)."""
+    return [(z * chunk, min(rows, (z + 1) * chunk)) for z in range(n)]
+
+
+def assert_slices_tile(rows, n, chunk):
+    """No slice is empty, and the slices tile [0, rows) (they are contiguous by construction)."""
+    assert n >= 1 and (n - 1) * chunk < rows <= n * chunk, (rows, n, chunk)
 
 
 def ctc_dlogits(seq_len, rng, T):

@@ -9,11 +9,15 @@ float64, the median member's, and the largest member's ratio to that median.
              whose pre-activation is within rounding of 0 flips between realisations and moves the gradient by a discrete amount
              (max / median up to 3e4 was measured that way), which no bar of a few rounding errors can absorb.
 factor = max(4, 1.5 x the largest ratio), for the forward and for the gradients separately.
+The same ensemble over CAP_GRAD_CASES (the shapes past the caps of the row reductions) gives "factor_cap" by the same rule, kept
+apart so that the factor of the cases above stays what it was derived from; its rows are under "cap".
 
 --hip (needs a GPU): the HIP path's err / e32 on the same cases, merged into the same file under "hip"; the default mode keeps an
-existing "hip" block.
+existing "hip" block.  The cap cases' rows go under "hip" / "cap_cases".
 
-    python tools/cnn_grad_accuracy.py [--draws 8] [--hip] [--out profiles/cnn_grad_accuracy.json]
+--cases grad | cap: only that list of cases; what the file holds for the other one is kept.
+
+    python tools/cnn_grad_accuracy.py [--draws 8] [--cases all|grad|cap] [--hip] [--out profiles/cnn_grad_accuracy.json]
 """
 import argparse
 import json
@@ -36,9 +40,10 @@ def spread(errs, norm):
     return {"norm": norm, "plain_err": errs[0], "median_err": med, "max_err": max(errs), "max_over_median": max(errs) / med if med > 0 else 0.0}
 
 
-def ensemble(draws):
+def ensemble(draws, case_list):
+    """-> (largest max / median of the forward and of the gradients, factors by the rule, rows per case)"""
     cases, largest = {}, {"forward": 0.0, "gradients": 0.0}
-    for kind, B, L in cc.GRAD_CASES:
+    for kind, B, L in case_list:
         spec, w, x, g = cc.grad_case(kind, B, L)
         pre = {}
         f64, g64 = cnn_ref.gradients(x, spec, w, g, torch.float64, pre=pre)
@@ -59,16 +64,20 @@ def ensemble(draws):
             largest[part] = max(largest[part], max(r["max_over_median"] for r in rows.values()))
         print(label, "largest max/median: forward %.3g, gradients %.3g" % (max(r["max_over_median"] for r in forward.values()),
                                                                           max(r["max_over_median"] for r in gradients.values())), flush=True)
+    return largest, {k: max(4.0, 1.5 * v) for k, v in largest.items()}, cases
+
+
+def method(draws):
     return {"method": "float32 realisations of tests/cnn_ref.py (plain + %d draws: channel orders of every product, batch order) against "
                       "float64; gradients under fixed ReLU masks (signs of the float64 pre-activations); per tensor the largest member "
                       "error over the median member's" % draws,
-            "draws": draws, "largest_max_over_median": largest,
-            "factor": {k: max(4.0, 1.5 * v) for k, v in largest.items()}, "cases": cases}
+            "draws": draws}
 
 
-def hip(factor):
+def hip(factor, case_list):
+    """-> (largest err / e32 above the floor, rows per case)"""
     out, worst = {}, 0.0
-    for kind, B, L in cc.GRAD_CASES:
+    for kind, B, L in case_list:
         spec, w, x, g = cc.grad_case(kind, B, L)
         fea, mom, dp, gu, masks = cc.hip_run(spec, w, x, g)
         label = "%s B%d L%d" % (kind, B, L)
@@ -77,29 +86,42 @@ def hip(factor):
         out[label] = {k: {"err_over_e32": r["ratio"], "err_rel": r["err_rel"], "e32_rel": r["e32_rel"], "ok": r["ok"]} for k, r in rows.items()}
         worst = max(worst, max(r["ratio"] for r in rows.values() if r["err_rel"] > cc.FLOOR))
         print(label, "largest err/e32 %.3g" % max(r["ratio"] for r in rows.values()), flush=True)
-    return {"note": "chiron_cnn_train_forward / _backward against the same float64 values, error over the plain float32 run's (e32); gradients "
-                    "under the HIP run's own ReLU masks; measured after the factors were fixed",
-            "largest_err_over_e32_above_the_floor": worst, "cases": out}
+    return worst, out
+
+
+HIP_NOTE = ("chiron_cnn_train_forward / _backward against the same float64 values, error over the plain float32 run's (e32); gradients "
+            "under the HIP run's own ReLU masks; measured after the factors were fixed")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--draws", type=int, default=8)
     ap.add_argument("--hip", action="store_true")
+    ap.add_argument("--cases", choices=["all", "grad", "cap"], default="all")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cnn_grad_accuracy.json"))
     a = ap.parse_args()
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     old = json.load(open(a.out)) if os.path.exists(a.out) else {}
+    out = old
     if a.hip:
-        if "factor" not in old or not isinstance(old["factor"], dict):
+        if not isinstance(old.get("factor"), dict) or (a.cases != "grad" and not isinstance(old.get("factor_cap"), dict)):
             raise SystemExit("run the CPU ensemble first: --hip reads its factors from %s" % a.out)
-        old["hip"] = hip(old["factor"])
-        out = old
+        h = out.setdefault("hip", {})
+        h["note"] = HIP_NOTE
+        if a.cases != "cap":
+            h["largest_err_over_e32_above_the_floor"], h["cases"] = hip(old["factor"], cc.GRAD_CASES)
+        if a.cases != "grad":
+            h["cap_largest_err_over_e32_above_the_floor"], h["cap_cases"] = hip(old["factor_cap"], cc.CAP_GRAD_CASES)
     else:
-        out = ensemble(a.draws)
-        if "hip" in old:
-            out["hip"] = old["hip"]
-        print("largest ratios %s -> factors %s" % (out["largest_max_over_median"], out["factor"]))
+        if a.cases != "cap":
+            out = dict(method(a.draws))
+            out["largest_max_over_median"], out["factor"], out["cases"] = ensemble(a.draws, cc.GRAD_CASES)
+            out.update({k: old[k] for k in ("factor_cap", "cap", "hip") if k in old})
+            print("largest ratios %s -> factors %s" % (out["largest_max_over_median"], out["factor"]))
+        if a.cases != "grad":
+            largest, out["factor_cap"], rows = ensemble(a.draws, cc.CAP_GRAD_CASES)
+            out["cap"] = {"draws": a.draws, "largest_max_over_median": largest, "cases": rows}
+            print("cap cases: largest ratios %s -> factor_cap %s" % (largest, out["factor_cap"]))
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
 

@@ -36,6 +36,10 @@ def main():
         sl = tc.ragged_seq_len(24, 60, rng)
         cases["saturated %s" % name] = tc.accuracy(spec, regimes.saturated_gate_weights(spec, name), fea, sl,
                                                    rng.normal(size=(24, 60, 5)).astype(np.float32))
+    # past the caps of the reductions over the rows (tests/train_cases.py, CAP_CASES)
+    for kind, B, T, what in tc.CAP_CASES:
+        spec, w, fea, sl, dl = tc.cap_case(kind, B, T)
+        cases["%s B=%d T=%d past the %s cap" % (kind, B, T, what)] = tc.accuracy(spec, w, fea, sl, dl)
     # the ratio says nothing where the float32 yardstick itself has lost the gradient (e32 of order 1: underflow of a saturated regime)
     worst = max(((c, n, r["ratio"]) for c, rows in cases.items() for n, r in rows.items()
                  if r["e32_rel"] < 0.01 and r["norm"] > 0), key=lambda x: x[2])
