@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """What does half precision cost THIS network, and where?  (BASELINE configs[4]; round-3 review, weak point 2.)
 
-CPU only, no kernel involved: the float64 oracle of oracle/nn_oracle.py is re-run with roundings inserted exactly where an
-f16 engine has them, one kind at a time, on trained-checkpoint-like weights with a peaked (trained-CTC-like) head:
+CPU only, no kernel involved: the float64 oracle of oracle/nn_oracle.py is re-run with roundings inserted where an f16
+engine stores halves (per kind of tensor; see `both` below), one kind at a time, on trained-checkpoint-like weights with a peaked (trained-CTC-like) head:
 
   weights     conv filters (BN folded in, as the engine stores them) and LSTM kernels rounded to f16
   activations every conv layer's output, the CNN features, every recurrent layer's h rounded to f16 (accumulation, z, gates,
               cell state, logits stay wide, as in the engine)
-  both        = what the f16 engine computes (up to accumulation order)
+  both        ~ what the f16 engine computes.  A STUDY of the formats, not the engine's arithmetic site by site: the engine does not
+              round block 1's conv2a filter / activation, conv2b filter (table form, pwl.hip) or signal branch, nor the stem's filter,
+              folds BN in fp32, stores z as halves in its unfused forms and writes the last layer's output as fp32.  The restatement
+              that follows the engine in detail, and that the kernels are tested against, is tests/f16_ref.py.
 
 and the two repairs the review proposed:
 
