@@ -20,6 +20,7 @@
 #include "../../include/chiron_amd.h"
 #include "kernels.h"
 #include "model_layout.h"
+#include "weight_pack.h"
 #include <dlfcn.h>
 
 // profiling buckets (chiron_engine_profile_read) = names of the roctx ranges (CHIRON_ROCTX); order = the PN_* enum below
@@ -77,8 +78,6 @@ extern "C" chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, 
   return CHIRON_OK;
 }
 
-static int roundup(int v, int m) { return (v + m - 1) / m * m; }
-
 extern "C" chiron_status chiron_weights_size(const chiron_model_desc* d, size_t* n_floats) {
   BlobMap map;
   chiron_status st = blob_map(d, &map);
@@ -94,29 +93,8 @@ extern "C" chiron_status chiron_weights_size(const chiron_model_desc* d, size_t*
 // Default form of the fp32 recurrence (DESIGN 3.2 has the same-box A/B figures behind the choice)
 #define CHIRON_LSTM_WIDE_DEFAULT 2
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-struct ConvGemmPlan {
-  // device weights for one fused GEMM
-  float* Wt = nullptr;
-  float* shift = nullptr;
-  float* descale = nullptr;   // dtype fp32-split: 2^-s[n] of the power-of-two row scaling (GemmParams::descale)
-  int N = 0, Npad = 0, K = 0;
-};
-
-// f16 engine, calibration (chiron_engine_calibrate): what a plan's weights lost when they were rounded to halves.
-// y[n] = sum_k x[k] f16(W[n][k]) = sum_k x[k] W[n][k] + sum_k x[k] dW[n][k]; the second sum's MEAN over the data, sum_k E[x_k] dW[n][k],
-// is a constant per output channel and is taken out of the plan's shift once the input channels' means are known.
-struct PlanHost {
-  std::vector<float> dW;       // [Npad][K]: (float)(_Float16)W - W of the BN-folded fp32 weight (0 in the K / N padding)
-  std::vector<float> shift0;   // the uncorrected shift
-  int N = 0, Npad = 0, K = 0;
-};
 struct CalibRecord {           // one measured input: columns [k0, k0 + cin) of the plan behind `shift`, or rows of an LSTM kernel
-  const float* shift;          // device shift array of the plan (key into plan_host), or the projection's for an LSTM layer
+  const float* shift;         // device shift array of the plan (key into plan_host), or the projection's for an LSTM layer
   int k0, cin;
   int lstm_layer, lstm_dir, lstm_part;   // lstm_layer >= 0: part 0 = x rows [k0, k0 + cin) of the TF kernel, part 1 = its h rows; dir -1 = both
   double rows;                 // rows summed
@@ -127,39 +105,6 @@ struct CalibCtx {
   size_t max_records = 0;
   std::vector<CalibRecord> rec;
   int skipped = 0;             // inputs that could not be measured (more than 256 channels, or more records than max_records)
-};
-
-struct BlockPlan {
-  bool lift = false;
-  int c_in = 0, c = 0, k = 0, stride = 1, left = 0;
-  int t_in = 0, t_out = 0;
-  float *lift_a = nullptr, *lift_b = nullptr;  // lift: conv2a folded scale/shift
-  float *res_a = nullptr, *res_b = nullptr;    // lift: branch1 folded scale and its own folded shift (kernels.h res_b)
-  // lift, population BN: conv2a + conv2b as a piecewise-linear table of the signal value (pwl.hip)
-  float *pwl_bp = nullptr, *pwl_ref = nullptr, *pwl_tab = nullptr, *pwl_shift = nullptr;
-  int pwl_nbp = 0;
-  ConvGemmPlan ga, gb, gc;                     // conv2a (non-lift), conv2b, conv2c(+conv1)
-  float* wino_u = nullptr;                     // conv2b in Winograd form (wino.hip): transformed filters [4 or 6][C][C], or null
-  int wino_f4 = 0;                             // 1: F(4,3) (six filters, length % 4 == 0), 0: F(2,3)
-  // bn_mode = batch (cnn.py:166-188): the GEMM weights above are raw, gc holds conv2c alone, g1 the 1x1 branch1 conv;
-  // scale / offset of the four BN sites (conv1 only when i_bn)
-  ConvGemmPlan g1;
-  bool i_bn = false;
-  float *bn_scale[4] = {nullptr, nullptr, nullptr, nullptr}, *bn_offset[4] = {nullptr, nullptr, nullptr, nullptr};  // conv1, 2a, 2b, 2c
-};
-
-struct LstmPlan {
-  int in_w = 0;
-  ConvGemmPlan proj[2];  // STACK / layer 0: proj[0] covers both directions; MULTI l>0: one per dir
-  int nproj = 1;
-  float* wfrag = nullptr;
-  void* wwide = nullptr;    // f16: recurrent weights in the 16x16x16 B-operand order of lstm16w_kernel
-  void* whfused = nullptr;  // f16: W_hh in the 16x16x32 order of lstm16f_kernel
-  void* wxwide = nullptr;   // f16: input weights in that order (lstm16f_kernel: projection fused into the recurrence)
-  int wx_ksteps = 0;        //      its k-steps of 16 (16: K = 256, 13: K = 200)
-  void* wsplit = nullptr;   // fp32-split: W_hh as hi + lo half pairs in the order of wwide (lstm32s_kernel)
-  float* wwide32 = nullptr; // fp32: recurrent weights in the 16x16x4 B-operand order of lstm32w_kernel
-  float* wlight = nullptr;  // K-split fragment of units 96..99 for the paired recurrence (fp32, H = 100)
 };
 
 struct ProfEvent {
@@ -237,11 +182,11 @@ struct Slot {
   } score;
 };
 
-struct chiron_engine {
+struct chiron_engine : NetPlans {   // T, C, the stem, blocks, lstm and the FC head: filled by build_plans
   chiron_model_desc desc;
   BlobMap map;                    // where desc puts every tensor of the weight blob
   chiron_engine_opts opts;
-  int L = 0, T = 0, C = 0, H = 0, K = 0;
+  int L = 0, H = 0, K = 0;
   int maxB = 0, BP = 0;
   bool stream32 = true;           // fp32: 1 x 1 convolutions on the weight-stationary streaming kernel (CHIRON_NO_STREAM32=1: gemm.hip, A/B switch)
   bool stream16 = true;           // f16: 1 x 1 convolutions on the streaming kernel (CHIRON_NO_STREAM16=1: gemm.hip, A/B switch)
@@ -262,12 +207,6 @@ struct chiron_engine {
   bool split = false;  // opts.dtype == CHIRON_F32_SPLIT: fp32 values as hi/lo half pairs on the f16 matrix cores (GEMMs only)
   int lasth_ld = 0;    // elements per lasth row (2H; split: rounded up to whole 32-element blocks)
   int kq = GEMM_BK;    // K padding quantum in elements: one LDS chunk = 128 bytes per row (32 floats / 64 halves)
-  // stem (HEAD RNA_model2 / RNA_model3): folded filter [k][C], shift [C]; batch-BN mode: raw filter + scale / offset
-  int stem_k = 0, stem_stride = 1, stem_left = 0, stem_t = 0, stem_c = 0;
-  float *stem_w = nullptr, *stem_shift = nullptr, *stem_scale = nullptr, *stem_offset = nullptr;
-  std::vector<BlockPlan> blocks;
-  std::vector<LstmPlan> lstm;
-  float *fc_w = nullptr, *fc_b = nullptr, *fc_wc = nullptr, *fc_bc = nullptr;
   std::vector<Slot> slots;
   std::map<const float*, PlanHost> plan_host;   // f16 engine: keyed by the plan's device shift pointer
   std::vector<float> host_weights;              // f16 engine: the caller's blob (LSTM kernels are read back from it in calibration)
@@ -285,510 +224,36 @@ static chiron_status dev_alloc(chiron_engine* e, void** p, size_t bytes, bool ze
   if (zero) HIP_TRY(hipMemset(*p, 0, bytes ? bytes : 16));
   return CHIRON_OK;
 }
-template <typename Tp>
-static chiron_status dev_upload(chiron_engine* e, Tp** p, const std::vector<Tp>& h) {
-  chiron_status st = dev_alloc(e, (void**)p, h.size() * sizeof(Tp), false);
-  if (st) return st;
-  HIP_TRY(hipMemcpy(*p, h.data(), h.size() * sizeof(Tp), hipMemcpyHostToDevice));
-  return CHIRON_OK;
-}
-
-// folded BN (cnn.py:125-163 population branch; association order of the .meta graph):
-//   inv = rsqrt(var + 1e-5) * scale ; y = x*inv + (offset - mean*inv)
-struct BnFold {
-  std::vector<float> inv, sh;
-};
-static BnFold fold_bn(const float* scale, const float* offset, const float* mean, const float* var, int n) {
-  BnFold f;
-  f.inv.resize(n);
-  f.sh.resize(n);
-  for (int i = 0; i < n; ++i) {
-    const float inv = (1.0f / sqrtf(var[i] + 1e-5f)) * scale[i];
-    f.inv[i] = inv;
-    f.sh[i] = offset[i] - mean[i] * inv;
-  }
-  return f;
-}
-
-static chiron_status upload_gemm(chiron_engine* e, ConvGemmPlan* g, const std::vector<float>& Wt, const std::vector<float>& shift, int N, int Npad, int K) {
-  g->N = N;
-  g->Npad = Npad;
-  g->K = K;
-  chiron_status st;
-  if (e->split) {
-    // per 32-element block of a row: 32 hi halves then 32 lo halves (K is a multiple of 32).  Row n is scaled by 2^s[n] so that its
-    // largest weight lies in [2^12, 2^13): hi <= 8192 is far from a half's 65504, and lo = O(2^-11 w) is a NORMAL half for every
-    // weight down to 2^-15 of the row's largest (GemmParams::descale).  CHIRON_SPLIT_NO_ROW_SCALE=1: the unscaled format of round 5 (A/B).
-    static const bool row_scale = getenv("CHIRON_SPLIT_NO_ROW_SCALE") == nullptr;
-    std::vector<_Float16> h(2 * Wt.size());
-    std::vector<float> sh2(shift), ds((size_t)Npad + 192, 1.0f);
-    for (int n = 0; n < Npad; ++n) {
-      float mx = 0.f;
-      for (int k = 0; k < K; ++k) mx = std::max(mx, fabsf(Wt[(size_t)n * K + k]));
-      int s = 0;
-      if (row_scale && mx > 0.f && std::isfinite(mx)) {
-        int ex;
-        frexpf(mx, &ex);                       // mx = f * 2^ex, 0.5 <= f < 1
-        s = std::min(60, std::max(-60, 13 - ex));
-        if (n < (int)sh2.size() && !std::isfinite(ldexpf(sh2[n], s))) s = 0;
-      }
-      ds[n] = ldexpf(1.0f, -s);
-      if (n < (int)sh2.size()) sh2[n] = ldexpf(sh2[n], s);
-      for (int k = 0; k < K; ++k) {
-        const size_t i = (size_t)n * K + k;
-        const float v = ldexpf(Wt[i], s);
-        const _Float16 hi = (_Float16)v;
-        const size_t blk = i / 32, el = i % 32;
-        h[blk * 64 + el] = hi;
-        h[blk * 64 + 32 + el] = (_Float16)(v - (float)hi);
-      }
-    }
-    _Float16* d = nullptr;
-    if ((st = dev_upload(e, &d, h))) return st;
-    g->Wt = reinterpret_cast<float*>(d);
-    if ((st = dev_upload(e, &g->descale, ds))) return st;
-    return dev_upload(e, &g->shift, sh2);
-  } else if (e->w2) {
-    // every row [K hi halves | K lo halves]: launch() runs the K-segments of a GEMM twice, the second time against the lo columns
-    std::vector<_Float16> h(2 * Wt.size());
-    for (int n = 0; n < Npad; ++n)
-      for (int k = 0; k < K; ++k) {
-        const float v = Wt[(size_t)n * K + k];
-        const _Float16 hi = (_Float16)v;
-        h[(size_t)n * 2 * K + k] = hi;
-        h[(size_t)n * 2 * K + K + k] = (_Float16)(v - (float)hi);
-      }
-    _Float16* d = nullptr;
-    if ((st = dev_upload(e, &d, h))) return st;
-    g->Wt = reinterpret_cast<float*>(d);
-  } else if (e->f16) {
-    std::vector<_Float16> h(Wt.size());
-    for (size_t i = 0; i < Wt.size(); ++i) h[i] = (_Float16)Wt[i];
-    _Float16* d = nullptr;
-    if ((st = dev_upload(e, &d, h))) return st;
-    g->Wt = reinterpret_cast<float*>(d);
-    if ((st = dev_upload(e, &g->shift, shift))) return st;
-    PlanHost& ph = e->plan_host[g->shift];
-    ph.dW.resize(Wt.size());
-    for (size_t i = 0; i < Wt.size(); ++i) ph.dW[i] = (float)h[i] - Wt[i];
-    ph.shift0 = shift;
-    ph.N = N, ph.Npad = Npad, ph.K = K;
-    return CHIRON_OK;
-  } else if ((st = dev_upload(e, &g->Wt, Wt))) {
-    return st;
-  }
-  return dev_upload(e, &g->shift, shift);
-}
-
-// Stem and residual blocks: BN folded into (population) or kept beside (batch) the weights, in the layouts the convolution kernels read
-static chiron_status plan_stem_and_blocks(chiron_engine* e, const float* w) {
-  const chiron_model_desc& d = e->desc;
-  const BlobMap& map = e->map;
-  const bool batch = e->bn_batch;
-  SiteFrames fr[MAX_SITES];
-  e->T = frames(map, e->L, fr);
-  e->C = d.blocks[d.n_blocks - 1].out_channels;
-  if (map.has_stem) {
-    const ConvSite& s = map.site[0];
-    const int k = s.k, co = s.co;
-    const float *Ws = w + s.w_off, *bn = w + s.bn_off;  // [k][1][co]
-    std::vector<float> wf((size_t)k * co), sh(co, 0.f);
-    chiron_status st;
-    if (batch) {
-      std::vector<float> sc(bn, bn + co), of(bn + co, bn + 2 * co);
-      for (size_t i = 0; i < wf.size(); ++i) wf[i] = Ws[i];
-      if ((st = dev_upload(e, &e->stem_scale, sc))) return st;
-      if ((st = dev_upload(e, &e->stem_offset, of))) return st;
-    } else {
-      const BnFold f = fold_bn(bn, bn + co, bn + 2 * co, bn + 3 * co, co);
-      for (int tap = 0; tap < k; ++tap)
-        for (int c = 0; c < co; ++c) wf[(size_t)tap * co + c] = Ws[(size_t)tap * co + c] * f.inv[c];
-      sh = f.sh;
-    }
-    if ((st = dev_upload(e, &e->stem_w, wf))) return st;
-    if ((st = dev_upload(e, &e->stem_shift, sh))) return st;
-    e->stem_k = k;
-    e->stem_stride = s.stride;
-    e->stem_c = co;
-    e->stem_t = fr[0].tout;
-    e->stem_left = fr[0].pad;
-  }
-  for (int bi = 0; bi < d.n_blocks; ++bi) {
-    const chiron_res_block& b = d.blocks[bi];
-    const ConvSite* site = map.site + map.has_stem + 4 * bi;   // site[SITE_BRANCH1 .. SITE_CONV2C]
-    const SiteFrames& f2 = fr[map.has_stem + 4 * bi + SITE_CONV2B];
-    BlockPlan bp;
-    bp.lift = b.in_channels == 1;
-    bp.c_in = b.in_channels;
-    bp.c = b.out_channels;
-    bp.k = b.k;
-    bp.stride = b.stride;
-    bp.t_in = f2.tin;
-    bp.t_out = f2.tout;
-    bp.left = f2.pad;
-    const int t = bp.t_in;
-    const int ci = b.in_channels, co = b.out_channels;
-    chiron_status st;
-    bp.i_bn = b.i_bn != 0;
-    // one BN site: population statistics fold into the weights; batch statistics leave the weights raw and keep
-    // scale / offset for bn_batch.hip
-    auto bn_site = [&](int which, BnFold* f) -> chiron_status {
-      const float* bn = w + site[which].bn_off;
-      if (batch) {
-        f->inv.assign(co, 1.0f);
-        f->sh.assign(co, 0.0f);
-        std::vector<float> sc(bn, bn + co), of(bn + co, bn + 2 * co);
-        chiron_status r = dev_upload(e, &bp.bn_scale[which], sc);
-        if (r == CHIRON_OK) r = dev_upload(e, &bp.bn_offset[which], of);
-        return r;
-      }
-      *f = fold_bn(bn, bn + co, bn + 2 * co, bn + 3 * co, co);
-      return CHIRON_OK;
-    };
-    const float *W1 = w + site[SITE_BRANCH1].w_off, *W2a = w + site[SITE_CONV2A].w_off, *W2b = w + site[SITE_CONV2B].w_off,
-                *W2c = w + site[SITE_CONV2C].w_off;
-    BnFold f1, f2a, f2b, f2c;
-    if (b.i_bn) {
-      if ((st = bn_site(SITE_BRANCH1, &f1))) return st;
-    } else {
-      f1.inv.assign(co, 1.0f);
-      f1.sh.assign(co, 0.0f);
-    }
-    if ((st = bn_site(SITE_CONV2A, &f2a))) return st;
-    if ((st = bn_site(SITE_CONV2B, &f2b))) return st;
-    if ((st = bn_site(SITE_CONV2C, &f2c))) return st;
-
-    const int Npad = roundup(co, GEMM_BN);
-    const int cop = roundup(co, e->kq);
-    // conv2b: Wt[n][tap*cop + c] = W2b[tap][c][n] * inv2b[n]
-    {
-      const int K = b.k * cop;
-      std::vector<float> Wt((size_t)Npad * K, 0.f), sh(Npad, 0.f);
-      for (int n = 0; n < co; ++n) {
-        for (int tap = 0; tap < b.k; ++tap)
-          for (int c = 0; c < co; ++c) Wt[(size_t)n * K + tap * cop + c] = W2b[((size_t)tap * co + c) * co + n] * f2b.inv[n];
-        sh[n] = f2b.sh[n];
-      }
-      if ((st = upload_gemm(e, &bp.gb, Wt, sh, co, Npad, K))) return st;
-      // 1 x 3, stride 1 over C = co channels, fp32, population BN, even length: Winograd F(2,3) (wino.hip) -- four
-      // products per output pair instead of six.  U_j[n][c] in float64 from the folded taps g_tap = W2b[tap][c][n]*inv[n].
-      if (!bp.lift && !batch && !e->f16 && !e->split && b.k == 3 && b.stride == 1 && (t % 2) == 0 && co % 64 == 0 && ci == co &&
-          getenv("CHIRON_NO_WINOGRAD") == nullptr) {
-        // F(4,3) from 256 frames per window on (round 6): its rounding error is correlated over the four frames of a quad and, measured
-        // against the float32 ensembles of tests/golden/parity_dist, costs the short strided topology more than it saves -- RNA_default
-        // (T = 100): typical window 1.32 .. 1.45 -> 1.13 .. 1.20 x the ensemble's median, tail 7 .. 9 % -> 2 .. 5 % with F(2,3), for 0.04 ms
-        // of its 1.7 ms batch; DNA_default (T = 400): parity within the noise of F(2,3)'s, F(4,3) worth 4.1 % of the headline.
-        // CHIRON_WINOGRAD_F4=1 / CHIRON_WINOGRAD_F2=1 force either form.
-        const bool f4 = (t % 4) == 0 && getenv("CHIRON_WINOGRAD_F2") == nullptr && (t >= 256 || getenv("CHIRON_WINOGRAD_F4") != nullptr);
-        const int nu = f4 ? 6 : 4;
-        // F(4,3): U = G g;  F(2,3): g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2
-        static const double G4[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                        {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-        static const double G2[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-        std::vector<float> U((size_t)nu * co * co);
-        for (int n = 0; n < co; ++n)
-          for (int c = 0; c < co; ++c) {
-            double gt[3];
-            for (int tap = 0; tap < 3; ++tap) gt[tap] = (double)W2b[((size_t)tap * co + c) * co + n] * f2b.inv[n];
-            for (int j = 0; j < nu; ++j) {
-              const double* gj = f4 ? G4[j] : G2[j];
-              U[((size_t)j * co + n) * co + c] = (float)(gj[0] * gt[0] + gj[1] * gt[1] + gj[2] * gt[2]);
-            }
-          }
-        bp.wino_f4 = f4 ? 1 : 0;
-        if ((st = dev_upload(e, &bp.wino_u, U))) return st;
-      }
-    }
-    if (bp.lift) {
-      std::vector<float> la(cop, 0.f), lb(cop, 0.f), ra(Npad, 0.f), rb(Npad, 0.f);
-      for (int c = 0; c < co; ++c) {
-        la[c] = W2a[c] * f2a.inv[c];
-        lb[c] = f2a.sh[c];
-        ra[c] = W1[c] * f1.inv[c];
-        rb[c] = e->f16 ? 0.f : f1.sh[c];   // the f16 engines keep round 4's arithmetic (shift folded): halves' rounding dominates there
-      }
-      if ((st = dev_upload(e, &bp.res_b, rb))) return st;
-      if ((st = dev_upload(e, &bp.lift_a, la))) return st;
-      if ((st = dev_upload(e, &bp.lift_b, lb))) return st;
-      if ((st = dev_upload(e, &bp.res_a, ra))) return st;
-      if (!batch && getenv("CHIRON_NO_PWL") == nullptr) {
-        // f[tap][n](s) = sum_c W2b'[tap][c][n] * relu(s*a[c] + b[c]) is piecewise linear in the signal value s:
-        // tabulate (alpha, beta) per interval between consecutive breakpoints -b[c]/a[c] (pwl.hip).  float64 sums.
-        std::vector<std::pair<double, int>> brk;  // (breakpoint, channel)
-        for (int c = 0; c < co; ++c)
-          if (la[c] != 0.f) brk.emplace_back(-(double)lb[c] / (double)la[c], c);
-        std::sort(brk.begin(), brk.end());
-        const int nb = (int)brk.size(), kk = b.k;
-        std::vector<double> al((size_t)kk * co, 0.0), be((size_t)kk * co, 0.0);
-        auto toggle = [&](int c, double sign) {
-          for (int tap = 0; tap < kk; ++tap)
-            for (int n = 0; n < co; ++n) {
-              const double wv = (double)(W2b[((size_t)tap * co + c) * co + n] * f2b.inv[n]) * sign;
-              al[(size_t)tap * co + n] += wv * (double)la[c];
-              be[(size_t)tap * co + n] += wv * (double)lb[c];
-            }
-        };
-        // s -> -inf: a channel is active iff a < 0, or a == 0 and b > 0
-        for (int c = 0; c < co; ++c)
-          if (la[c] < 0.f || (la[c] == 0.f && lb[c] > 0.f)) toggle(c, 1.0);
-        std::vector<float> tab((size_t)(nb + 1) * kk * co * 2), bpf(std::max(nb, 1), 0.f), reff(nb + 1, 0.f);
-        for (int iv = 0; iv < nb; ++iv) bpf[iv] = (float)brk[iv].first;   // may round to +-inf: such a breakpoint is simply never crossed
-        for (int iv = 0; iv <= nb; ++iv) {
-          if (iv > 0) {
-            const int c = brk[iv - 1].second;
-            toggle(c, la[c] > 0.f ? 1.0 : -1.0);  // crossing its breakpoint upwards switches a channel on (a > 0) or off (a < 0)
-          }
-          // The table stores the slope and the value at a reference point of the interval, f = alpha*(s - ref) + f(ref).
-          // ref = the point of the interval nearest to 0 (0 itself when the interval contains it): |s - ref| <= |s| for
-          // every s the interval can receive, so a breakpoint far outside the signal range (a near-dead channel: tiny
-          // folded scale, breakpoint at -1e6 or beyond float range) never makes alpha*(s - ref) cancel against f(ref).
-          const double lower = iv > 0 ? (double)bpf[iv - 1] : -(double)INFINITY, upper = iv < nb ? (double)bpf[iv] : (double)INFINITY;
-          double ref = std::min(std::max(0.0, lower), upper);
-          ref = std::min(std::max(ref, -(double)FLT_MAX), (double)FLT_MAX);
-          reff[iv] = (float)ref;
-          for (size_t i = 0; i < (size_t)kk * co; ++i) {
-            tab[((size_t)iv * kk * co + i) * 2] = (float)al[i];
-            tab[((size_t)iv * kk * co + i) * 2 + 1] = (float)(al[i] * (double)reff[iv] + be[i]);
-          }
-        }
-        std::vector<float> sh2(f2b.sh.begin(), f2b.sh.begin() + co);
-        bp.pwl_nbp = nb;
-        if ((st = dev_upload(e, &bp.pwl_bp, bpf))) return st;
-        if ((st = dev_upload(e, &bp.pwl_ref, reff))) return st;
-        if ((st = dev_upload(e, &bp.pwl_tab, tab))) return st;
-        if ((st = dev_upload(e, &bp.pwl_shift, sh2))) return st;
-      }
-      // conv2c; the signal branch (scale res_a, shift res_b) is evaluated by the epilogue as one fmaf and added to the finished sum
-      // (batch-statistics BN: both fold to 1 / 0 here and the branch is normalised by bn_batch.hip)
-      const int K = cop;
-      std::vector<float> Wt((size_t)Npad * K, 0.f), sh(Npad, 0.f);
-      for (int n = 0; n < co; ++n) {
-        for (int c = 0; c < co; ++c) Wt[(size_t)n * K + c] = W2c[(size_t)c * co + n] * f2c.inv[n];
-        sh[n] = e->f16 ? f2c.sh[n] + f1.sh[n] : f2c.sh[n];
-      }
-      if ((st = upload_gemm(e, &bp.gc, Wt, sh, co, Npad, K))) return st;
-    } else {
-      const int cip = roundup(ci, e->kq);
-      {
-        const int K = cip;
-        std::vector<float> Wt((size_t)Npad * K, 0.f), sh(Npad, 0.f);
-        for (int n = 0; n < co; ++n) {
-          for (int c = 0; c < ci; ++c) Wt[(size_t)n * K + c] = W2a[(size_t)c * co + n] * f2a.inv[n];
-          sh[n] = f2a.sh[n];
-        }
-        if ((st = upload_gemm(e, &bp.ga, Wt, sh, co, Npad, K))) return st;
-      }
-      if (batch) {
-        // separate GEMMs: each branch is normalised with its own batch statistics before the add
-        {
-          const int K = cop;
-          std::vector<float> Wt((size_t)Npad * K, 0.f), sh(Npad, 0.f);
-          for (int n = 0; n < co; ++n)
-            for (int c = 0; c < co; ++c) Wt[(size_t)n * K + c] = W2c[(size_t)c * co + n];
-          if ((st = upload_gemm(e, &bp.gc, Wt, sh, co, Npad, K))) return st;
-        }
-        {
-          const int K = cip;
-          std::vector<float> Wt((size_t)Npad * K, 0.f), sh(Npad, 0.f);
-          for (int n = 0; n < co; ++n)
-            for (int c = 0; c < ci; ++c) Wt[(size_t)n * K + c] = W1[(size_t)c * co + n];
-          if ((st = upload_gemm(e, &bp.g1, Wt, sh, co, Npad, K))) return st;
-        }
-      } else {
-        // conv2c and branch1/conv1 fused along K: [conv2b output | block input]
-        const int K = cop + cip;
-        std::vector<float> Wt((size_t)Npad * K, 0.f), sh(Npad, 0.f);
-        for (int n = 0; n < co; ++n) {
-          for (int c = 0; c < co; ++c) Wt[(size_t)n * K + c] = W2c[(size_t)c * co + n] * f2c.inv[n];
-          for (int c = 0; c < ci; ++c) Wt[(size_t)n * K + cop + c] = W1[(size_t)c * co + n] * f1.inv[n];
-          sh[n] = f2c.sh[n] + f1.sh[n];
-        }
-        if ((st = upload_gemm(e, &bp.gc, Wt, sh, co, Npad, K))) return st;
-      }
-    }
-    e->blocks.push_back(bp);
+// What the packer (weight_pack.h) prepared, onto the device: allocate, copy, store the plan's pointer; an f16 GEMM's host record goes
+// under its device shift pointer
+static chiron_status upload_plans(chiron_engine* e, std::vector<Upload>& ups) {
+  for (Upload& u : ups) {
+    chiron_status st = dev_alloc(e, u.dst, u.bytes, false);
+    if (st) return st;
+    HIP_TRY(hipMemcpy(*u.dst, u.data, u.bytes, hipMemcpyHostToDevice));
+    u.owner.reset();
+    if (u.host.Npad > 0) e->plan_host[(const float*)*u.dst] = std::move(u.host);
   }
   return CHIRON_OK;
 }
 
-// One LSTM layer from the TF kernels kern[dir] [in_w + H][4H] and biases bias[dir] [4H]: the x-projection GEMMs and W_hh in the
-// operand order of every recurrence kernel the dtype can run.  z column n of a direction: gate = n / H, unit = n % H (the order
-// of the TF kernel's columns).
-static chiron_status plan_lstm_layer(chiron_engine* e, int l, const float* const kern[2], const float* const bias[2]) {
-  const chiron_model_desc& d = e->desc;
-  const int H = d.hidden;
-  const int zc = 4 * H;
-  LstmPlan lp;
-  lp.in_w = e->map.lstm_in[l];
-  // kern[dir][k_off + k][g * H + unit], 0 outside the width x H matrix that starts at row k_off; W_hh is the H rows below W_x's in_w
-  auto wat = [&](int dir, int k_off, int width, int k, int g, int unit) -> float {
-    return k < width && unit < H ? kern[dir][(size_t)(k_off + k) * 4 * H + g * H + unit] : 0.f;
-  };
-  auto whh = [&](int dir, int k, int g, int unit) -> float { return wat(dir, lp.in_w, H, k, g, unit); };
-  const bool split = d.rnn_kind == CHIRON_RNN_MULTI && l > 0;
-  lp.nproj = split ? 2 : 1;
-  const int Kp = roundup(lp.in_w, e->kq);
-  chiron_status st;
-  for (int pj = 0; pj < lp.nproj; ++pj) {
-    const int ndir = split ? 1 : 2;
-    const int N = ndir * zc;
-    const int Npad = std::max(roundup(N, GEMM_BN), roundup(N, 160));  // the DMA kernel reads whole 160-row weight tiles
-    std::vector<float> Wt((size_t)Npad * Kp, 0.f), sh(Npad, 0.f);
-    for (int n = 0; n < N; ++n) {
-      const int dir = split ? pj : n / zc;
-      const int nl = n % zc;
-      const int g = nl / H, unit = nl % H;
-      for (int k = 0; k < lp.in_w; ++k) Wt[(size_t)n * Kp + k] = kern[dir][(size_t)k * 4 * H + g * H + unit];
-      // forget_bias = 1.0 (TF LSTMCell default; Add(+1.0) const in the .meta while-body) folded here
-      sh[n] = bias[dir][g * H + unit] + (g == 2 ? 1.0f : 0.0f);
-    }
-    if ((st = upload_gemm(e, &lp.proj[pj], Wt, sh, N, Npad, Kp))) return st;
-  }
-  // recurrent weights in MFMA B-operand order: [dir][wave][k][lane], lane = gate*16 + (unit & 15)
-  std::vector<float> wf((size_t)2 * LSTM_NW * LSTM_K * 64, 0.f);
-  for (int dir = 0; dir < 2; ++dir)
-    for (int wv = 0; wv < LSTM_NW; ++wv)
-      for (int k = 0; k < LSTM_K; ++k)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int g = lane >> 4, unit = 16 * wv + (lane & 15);
-          wf[(((size_t)dir * LSTM_NW + wv) * LSTM_K + k) * 64 + lane] = whh(dir, k, g, unit);
-        }
-  if (e->f16) {
-    // v_mfma_f32_4x4x4_16B_f16 B-operand order: [dir][wave][k-step j][lane][4 halves], k = 4j .. 4j+3
-    std::vector<_Float16> wh((size_t)2 * LSTM_NW * LSTM_KSTEPS16 * 64 * 4, (_Float16)0.f);
-    for (int dir = 0; dir < 2; ++dir)
-      for (int wv = 0; wv < LSTM_NW; ++wv)
-        for (int j = 0; j < LSTM_KSTEPS16; ++j)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int q = 0; q < 4; ++q) {
-              const int k = 4 * j + q, g = lane >> 4, unit = 16 * wv + (lane & 15);
-              wh[((((size_t)dir * LSTM_NW + wv) * LSTM_KSTEPS16 + j) * 64 + lane) * 4 + q] = (_Float16)whh(dir, k, g, unit);
-            }
-    _Float16* d16 = nullptr;
-    if ((st = dev_upload(e, &d16, wh))) return st;
-    lp.wfrag = reinterpret_cast<float*>(d16);
-    if (H == 100) {
-      // lstm16w_kernel: [dir][wave 8][slot 4][k-step 7][lane][4 halves]; lane = kq*16 + 4u + gate, tile = 3 wave + slot
-      std::vector<_Float16> ww((size_t)2 * 8 * 4 * 7 * 64 * 4, (_Float16)0.f);
-      for (int dir = 0; dir < 2; ++dir)
-        for (int wv = 0; wv < 8; ++wv)
-          for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
-            for (int ks = 0; ks < 7; ++ks)
-              for (int lane = 0; lane < 64; ++lane)
-                for (int q = 0; q < 4; ++q) {
-                  const int k = 16 * ks + 4 * (lane >> 4) + q, g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
-                  ww[(((((size_t)dir * 8 + wv) * 4 + slot) * 7 + ks) * 64 + lane) * 4 + q] = (_Float16)whh(dir, k, g, unit);
-                }
-      _Float16* dw = nullptr;
-      if ((st = dev_upload(e, &dw, ww))) return st;
-      lp.wwide = dw;
-      if (lp.nproj == 1 && (lp.in_w == 256 || lp.in_w == 200)) {
-        // lstm16f_kernel (v_mfma_f32_16x16x32_f16): W_x and W_hh as [dir][wave][slot][k-step of 32][lane][8 halves],
-        // lane = kg*16 + 4u + gate -> k = 32 ks + 8 kg + e, column gate*H + 4 (3 wave + slot) + u; zero past the width
-        const int ksx = lp.in_w == 256 ? 8 : 7;
-        auto frag = [&](int ksteps, int k_off, int width) {
-          std::vector<_Float16> v((size_t)2 * 8 * 4 * ksteps * 64 * 8, (_Float16)0.f);
-          for (int dir = 0; dir < 2; ++dir)
-            for (int wv = 0; wv < 8; ++wv)
-              for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
-                for (int ks = 0; ks < ksteps; ++ks)
-                  for (int lane = 0; lane < 64; ++lane)
-                    for (int q = 0; q < 8; ++q) {
-                      const int k = 32 * ks + 8 * (lane >> 4) + q, g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
-                      v[(((((size_t)dir * 8 + wv) * 4 + slot) * ksteps + ks) * 64 + lane) * 8 + q] = (_Float16)wat(dir, k_off, width, k, g, unit);
-                    }
-          return v;
-        };
-        _Float16 *dx = nullptr, *dh = nullptr;
-        if ((st = dev_upload(e, &dx, frag(ksx, 0, lp.in_w)))) return st;
-        if ((st = dev_upload(e, &dh, frag(4, lp.in_w, H)))) return st;
-        lp.wxwide = dx;
-        lp.whfused = dh;
-        lp.wx_ksteps = ksx;
-      }
-    }
-  } else if ((st = dev_upload(e, &lp.wfrag, wf))) {
-    return st;
-  }
-  if (e->w2 && H != 100) return fail(CHIRON_ERR_INVALID, "dtype f16-w2: the recurrence kernel is built for hidden=100");
-  if ((e->w2 || (e->split && getenv("CHIRON_SPLIT_REC32") == nullptr)) && H == 100) {
-    // lstm32s_kernel: [hi | lo][dir][wave 8][slot 4][k-step 7][lane][4 halves]; lane = kq*16 + 4u + gate, tile = 3 wave + slot (the order
-    // of lstm16w_kernel's fragments), every weight as an exact hi + lo half pair
-    const size_t half = (size_t)2 * 8 * 4 * 7 * 64 * 4;
-    std::vector<_Float16> ws(2 * half, (_Float16)0.f);
-    for (int dir = 0; dir < 2; ++dir)
-      for (int wv = 0; wv < 8; ++wv)
-        for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
-          for (int ks = 0; ks < 7; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int q = 0; q < 4; ++q) {
-                const int k = 16 * ks + 4 * (lane >> 4) + q, g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
-                const float wv32 = whh(dir, k, g, unit);
-                const _Float16 hi = (_Float16)wv32;
-                const size_t at = (((((size_t)dir * 8 + wv) * 4 + slot) * 7 + ks) * 64 + lane) * 4 + q;
-                ws[at] = hi;
-                ws[half + at] = (_Float16)(wv32 - (float)hi);
-              }
-    _Float16* dws = nullptr;
-    if ((st = dev_upload(e, &dws, ws))) return st;
-    lp.wsplit = dws;
-  }
-  if (!e->f16) {
-    // light-wave fragment of lstm_pair_kernel: [dir][m = 4q + a][lane = kg*16 + gate*4 + j] = W_hh[16q + 4kg + a][gate*H + 96 + j]
-    std::vector<float> wl((size_t)2 * 28 * 64, 0.f);
-    for (int dir = 0; dir < 2; ++dir)
-      for (int m = 0; m < 28; ++m)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int q = m >> 2, a = m & 3, kg = lane >> 4, g = (lane >> 2) & 3, j = lane & 3;
-          const int k = 16 * q + 4 * kg + a;
-          wl[((size_t)dir * 28 + m) * 64 + lane] = whh(dir, k, g, 96 + j);
-        }
-    if ((st = dev_upload(e, &lp.wlight, wl))) return st;
-    if (H == 100) {
-      // lstm32w_kernel: [dir][wave 8][slot 4][k-step 25][lane]; lane = kq*16 + 4u + gate, tile = 3 wave + slot
-      std::vector<float> ww((size_t)2 * 8 * 4 * 25 * 64, 0.f);
-      for (int dir = 0; dir < 2; ++dir)
-        for (int wv = 0; wv < 8; ++wv)
-          for (int slot = 0; slot < (wv == 7 ? 4 : 3); ++slot)
-            for (int ks = 0; ks < 25; ++ks)
-              for (int lane = 0; lane < 64; ++lane) {
-                const int k = 4 * ks + (lane >> 4), g = lane & 3, unit = 4 * (3 * wv + slot) + ((lane >> 2) & 3);
-                ww[((((size_t)dir * 8 + wv) * 4 + slot) * 25 + ks) * 64 + lane] = whh(dir, k, g, unit);
-              }
-      if ((st = dev_upload(e, &lp.wwide32, ww))) return st;
-    }
-  }
-  e->lstm.push_back(lp);
-  return CHIRON_OK;
-}
-
-// FC head (raw)
-static chiron_status plan_head(chiron_engine* e, const float* w) {
-  const BlobMap& m = e->map;
-  chiron_status st;
-  if ((st = dev_upload(e, &e->fc_w, std::vector<float>(w + m.head_w, w + m.head_b)))) return st;
-  if ((st = dev_upload(e, &e->fc_b, std::vector<float>(w + m.head_b, w + m.head_wc)))) return st;
-  if ((st = dev_upload(e, &e->fc_wc, std::vector<float>(w + m.head_wc, w + m.head_bc)))) return st;
-  return dev_upload(e, &e->fc_bc, std::vector<float>(w + m.head_bc, w + m.total));
+static bool split_row_scale() {   // read once per process, by the first fp32-split engine
+  static const bool on = getenv("CHIRON_SPLIT_NO_ROW_SCALE") == nullptr;
+  return on;
 }
 
 static chiron_status build_plans(chiron_engine* e, const float* w) {
-  const chiron_model_desc& d = e->desc;
-  e->bn_batch = d.bn_mode == CHIRON_BN_BATCH;
-  if (e->bn_batch && (e->f16 || e->split)) return fail(CHIRON_ERR_INVALID, "bn_mode=batch is implemented for dtype f32 only");
-  if (e->f16 || e->split) {
-    for (int bi = 0; bi < d.n_blocks; ++bi)
-      if (d.blocks[bi].out_channels % GEMM_BN || (d.blocks[bi].in_channels != 1 && d.blocks[bi].in_channels % 64))
-        return fail(CHIRON_ERR_INVALID, "dtype f16: block %d has %d -> %d channels; the f16 kernels need multiples of 64 / 128", bi,
-                    d.blocks[bi].in_channels, d.blocks[bi].out_channels);
-  }
-  chiron_status st = plan_stem_and_blocks(e, w);
-  for (int l = 0; l < d.rnn_layers && st == CHIRON_OK; ++l) {
-    const float* const kern[2] = {w + e->map.lstm_kernel[l][0], w + e->map.lstm_kernel[l][1]};
-    const float* const bias[2] = {w + e->map.lstm_bias[l][0], w + e->map.lstm_bias[l][1]};
-    st = plan_lstm_layer(e, l, kern, bias);
-  }
-  return st ? st : plan_head(e, w);
+  e->bn_batch = e->desc.bn_mode == CHIRON_BN_BATCH;
+  PackSwitches sw;
+  sw.no_winograd = getenv("CHIRON_NO_WINOGRAD") != nullptr;
+  sw.wino_f2 = getenv("CHIRON_WINOGRAD_F2") != nullptr;
+  sw.wino_f4 = getenv("CHIRON_WINOGRAD_F4") != nullptr;
+  sw.no_pwl = getenv("CHIRON_NO_PWL") != nullptr;
+  sw.split_rec32 = getenv("CHIRON_SPLIT_REC32") != nullptr;
+  if (e->split) sw.split_row_scale = split_row_scale();
+  std::vector<Upload> ups;
+  const chiron_status st = pack_weights(e->desc, e->map, w, e->L, e->opts.dtype, sw, e, &ups);
+  return st ? st : upload_plans(e, ups);
 }
 
 // ---- sizes of an engine, computable without a GPU: the frame count, the largest tensor a kernel addresses with a
@@ -1077,19 +542,41 @@ struct Prof {
   }
 };
 
-static void init_gemm(GemmParams* g, const chiron_engine* e, const ConvGemmPlan& w, int B) {
-  memset(g, 0, sizeof(*g));
-  g->B = B;
-  g->BP = e->BP;
-  g->N = w.N;
-  g->K = w.K;
-  g->Wt = w.Wt;
-  g->shift = w.shift;
-  g->descale = w.descale;
-  g->z_dirs_total = 2;
+// The K-segments of one GEMM, in ELEMENTS; the f16 kernels address in 4-byte units (see GemmParams::f16)
+struct Segs {
+  GemmSeg s[GEMM_MAX_SEG];
+  int n = 0;
+  Segs(std::initializer_list<GemmSeg> l) {
+    for (const GemmSeg& g : l) s[n++] = g;
+  }
+  // the k taps of a 1 x k convolution over src [.][C], each tap a segment `cop` columns wide
+  Segs(const float* src, int C, int cop, int t_in, int stride, int k, int left) {
+    for (int j = 0; j < k; ++j) s[n++] = GemmSeg{src, C, 0, C, cop, t_in, stride, j - left, 0};
+  }
+};
+
+// The launch descriptor of plan w over M output rows of T_out frames per window, written to out [M][ldo]; everything else zero
+static GemmParams gemm_desc(const chiron_engine* e, const ConvGemmPlan& w, int B, long M, int T_out, const Segs& segs, int relu, float* out, int ldo) {
+  GemmParams g;
+  memset(&g, 0, sizeof(g));
+  g.B = B;
+  g.BP = e->BP;
+  g.N = w.N;
+  g.K = w.K;
+  g.Wt = w.Wt;
+  g.shift = w.shift;
+  g.descale = w.descale;
+  g.z_dirs_total = 2;
+  g.M = (int)M;
+  g.T_out = T_out;
+  g.nseg = segs.n;
+  for (int i = 0; i < segs.n; ++i) g.seg[i] = segs.s[i];
+  g.relu = relu;
+  g.out = out;
+  g.ldo = ldo;
+  return g;
 }
 
-// Segments are filled in ELEMENTS; the f16 kernels address in 4-byte units (see GemmParams::f16).
 // Calibration pass of the f16 engine: before a convolution GEMM runs, the column sums of every K-segment's source.
 static void calib_measure(chiron_engine* e, const float* shift, int k0, const void* src, long rows, int ld, int col0, int cin, int BP, int B,
                           int lstm_layer, int lstm_dir, int lstm_part, hipStream_t stream) {
@@ -1168,54 +655,30 @@ static bool run_cnn_batch_bn(chiron_engine* e, Slot* s, int B, const float* sig)
     const long Min = (long)B * b.t_in, Mout = (long)B * b.t_out;
     double* s0 = s->bn_sums;
     double* s1 = s->bn_sums + 2 * C;
-    GemmParams g;
+    const Segs in_taps(A, C, cop, b.t_in, b.stride, b.k, b.left);
     Prof pr(e, s, PN_CONV, 2.0 * ((double)Min * b.c_in * C + (double)Mout * (b.k * C + C + b.c_in) * C), 4.0 * (Min + 3.0 * Mout) * C * 3);
     // conv2a + BN + ReLU
     if (b.lift) {
       launch_rank1_conv(sig, b.lift_a, A, Min, b.t_in, e->L, 1, C, true, s->stream);   // BN follows: centered (bn_batch.hip)
     } else {
-      init_gemm(&g, e, b.ga, B);
-      g.M = (int)Min;
-      g.T_out = b.t_in;
-      g.nseg = 1;
-      g.seg[0] = GemmSeg{x, b.c_in, 0, b.c_in, roundup(b.c_in, e->kq), b.t_in, 1, 0, 0};
-      g.out = A;
-      g.ldo = C;
+      GemmParams g = gemm_desc(e, b.ga, B, Min, b.t_in, {GemmSeg{x, b.c_in, 0, b.c_in, roundup(b.c_in, e->kq), b.t_in, 1, 0, 0}}, 0, A, C);
       ok &= launch(e, g, s->stream);
     }
     launch_bn_stats(A, Min, C, s0, s->stream);
     launch_bn_apply(A, s0, b.bn_scale[1], b.bn_offset[1], Min, C, 1, nullptr, nullptr, nullptr, nullptr, s->stream);
     // conv2b + BN + ReLU
-    init_gemm(&g, e, b.gb, B);
-    g.M = (int)Mout;
-    g.T_out = b.t_out;
-    g.nseg = b.k;
-    for (int j = 0; j < b.k; ++j) g.seg[j] = GemmSeg{A, C, 0, C, cop, b.t_in, b.stride, j - b.left, 0};
-    g.out = Bf;
-    g.ldo = C;
+    GemmParams g = gemm_desc(e, b.gb, B, Mout, b.t_out, in_taps, 0, Bf, C);
     ok &= launch(e, g, s->stream);
     launch_bn_stats(Bf, Mout, C, s0, s->stream);
     launch_bn_apply(Bf, s0, b.bn_scale[2], b.bn_offset[2], Mout, C, 1, nullptr, nullptr, nullptr, nullptr, s->stream);
     // conv2c (+ BN), branch1 conv1 (+ BN iff i_bn), add, ReLU
-    init_gemm(&g, e, b.gc, B);
-    g.M = (int)Mout;
-    g.T_out = b.t_out;
-    g.nseg = 1;
-    g.seg[0] = GemmSeg{Bf, C, 0, C, cop, b.t_out, 1, 0, 0};
-    g.out = Cf;
-    g.ldo = C;
+    g = gemm_desc(e, b.gc, B, Mout, b.t_out, {GemmSeg{Bf, C, 0, C, cop, b.t_out, 1, 0, 0}}, 0, Cf, C);
     ok &= launch(e, g, s->stream);
     launch_bn_stats(Cf, Mout, C, s0, s->stream);
     if (b.lift) {
       launch_rank1_conv(sig, b.res_a, D, Mout, b.t_out, e->L, b.stride, C, b.i_bn, s->stream);
     } else {
-      init_gemm(&g, e, b.g1, B);
-      g.M = (int)Mout;
-      g.T_out = b.t_out;
-      g.nseg = 1;
-      g.seg[0] = GemmSeg{x, b.c_in, 0, b.c_in, roundup(b.c_in, e->kq), b.t_in, b.stride, 0, 0};
-      g.out = D;
-      g.ldo = C;
+      g = gemm_desc(e, b.g1, B, Mout, b.t_out, {GemmSeg{x, b.c_in, 0, b.c_in, roundup(b.c_in, e->kq), b.t_in, b.stride, 0, 0}}, 0, D, C);
       ok &= launch(e, g, s->stream);
     }
     if (b.i_bn) launch_bn_stats(D, Mout, C, s1, s->stream);
@@ -1250,16 +713,9 @@ static bool run_cnn(chiron_engine* e, Slot* s, int B, const float* sig) {
     }
     float* bufA = s->act[ia];
     float* bufB = s->act[ib];
-    GemmParams g;
+    const long Mout = (long)B * b.t_out;
+    const Segs in_taps(bufA, b.c, cop, b.t_in, b.stride, b.k, b.left);   // conv2b reads conv2a's output from bufA
     if (b.lift) {
-      // conv2b over the lifted signal: A(m, tap*C + c) = relu(sig*a[c] + b[c])
-      init_gemm(&g, e, b.gb, B);
-      g.M = B * b.t_out;
-      g.T_out = b.t_out;
-      g.nseg = b.k;
-      g.relu = 1;
-      g.out = bufB;
-      g.ldo = b.c;
       bool done_pwl = false;
       if (b.pwl_tab != nullptr) {
         // conv2a + conv2b in one memory-bound pass over a piecewise-linear table of the signal value (pwl.hip)
@@ -1276,24 +732,18 @@ static bool run_cnn(chiron_engine* e, Slot* s, int B, const float* sig) {
           Prof pr(e, s, PN_LIFT, 2.0 * B * b.t_in * b.c, 4.0 * B * b.t_in + (e->f16 ? 2.0 : 4.0) * B * b.t_in * b.c);
           launch_lift(sig, b.lift_a, b.lift_b, bufA, (long)B * b.t_in, b.c, e->f16 ? 1 : e->split ? 2 : 0, s->stream);
         }
-        for (int j = 0; j < b.k; ++j) g.seg[j] = GemmSeg{bufA, b.c, 0, b.c, cop, b.t_in, b.stride, j - b.left, 0};
+        // conv2b over the lifted signal: A(m, tap*C + c) = relu(sig*a[c] + b[c])
+        GemmParams g = gemm_desc(e, b.gb, B, Mout, b.t_out, in_taps, 1, bufB, b.c);
         Prof pr(e, s, PN_CONV, 2.0 * B * b.t_out * (double)b.k * b.c * b.c, (e->f16 ? 2.0 : 4.0) * B * (b.t_in + b.t_out) * b.c);
         ok &= launch(e, g, s->stream);
       }
       // conv2c + lifted branch1 + ReLU
-      init_gemm(&g, e, b.gc, B);
-      g.M = B * b.t_out;
-      g.T_out = b.t_out;
-      g.nseg = 1;
-      g.seg[0] = GemmSeg{bufB, b.c, 0, b.c, cop, b.t_out, 1, 0, 0};
-      g.relu = 1;
+      GemmParams g = gemm_desc(e, b.gc, B, Mout, b.t_out, {GemmSeg{bufB, b.c, 0, b.c, cop, b.t_out, 1, 0, 0}}, 1, bufA, b.c);
       g.sig = sig;
       g.L = e->L;
       g.res_a = b.res_a;
       g.res_b = b.res_b;
       g.res_stride = b.stride;
-      g.out = bufA;
-      g.ldo = b.c;
       {
         Prof pr(e, s, PN_RES, 2.0 * B * b.t_out * (double)b.c * b.c, 8.0 * B * b.t_out * b.c);
         ok &= launch(e, g, s->stream);
@@ -1303,28 +753,14 @@ static bool run_cnn(chiron_engine* e, Slot* s, int B, const float* sig) {
     } else {
       const int cip = roundup(b.c_in, e->kq);
       // conv2a
-      init_gemm(&g, e, b.ga, B);
-      g.M = B * b.t_in;
-      g.T_out = b.t_in;
-      g.nseg = 1;
-      g.seg[0] = GemmSeg{x, b.c_in, 0, b.c_in, cip, b.t_in, 1, 0, 0};
-      g.relu = 1;
-      g.out = bufA;
-      g.ldo = b.c;
+      GemmParams g = gemm_desc(e, b.ga, B, (long)B * b.t_in, b.t_in, {GemmSeg{x, b.c_in, 0, b.c_in, cip, b.t_in, 1, 0, 0}}, 1, bufA, b.c);
       {
         // conv2a (K = c_in) has its own bucket: on the fp32 engine it runs on the streaming kernel (stream32.hip)
         Prof pr(e, s, PN_CONV2A, 2.0 * B * b.t_in * (double)b.c_in * b.c, 4.0 * B * b.t_in * (b.c_in + b.c));
         ok &= launch(e, g, s->stream);
       }
       // conv2b
-      init_gemm(&g, e, b.gb, B);
-      g.M = B * b.t_out;
-      g.T_out = b.t_out;
-      g.nseg = b.k;
-      for (int j = 0; j < b.k; ++j) g.seg[j] = GemmSeg{bufA, b.c, 0, b.c, cop, b.t_in, b.stride, j - b.left, 0};
-      g.relu = 1;
-      g.out = bufB;
-      g.ldo = b.c;
+      g = gemm_desc(e, b.gb, B, Mout, b.t_out, in_taps, 1, bufB, b.c);
       {
         bool done = false;
         if (b.wino_u != nullptr) {
@@ -1342,15 +778,8 @@ static bool run_cnn(chiron_engine* e, Slot* s, int B, const float* sig) {
         }
       }
       // conv2c + branch1/conv1 fused along K, + ReLU
-      init_gemm(&g, e, b.gc, B);
-      g.M = B * b.t_out;
-      g.T_out = b.t_out;
-      g.nseg = 2;
-      g.seg[0] = GemmSeg{bufB, b.c, 0, b.c, cop, b.t_out, 1, 0, 0};
-      g.seg[1] = GemmSeg{x, b.c_in, 0, b.c_in, cip, b.t_in, b.stride, 0, 0};
-      g.relu = 1;
-      g.out = bufA;
-      g.ldo = b.c;
+      g = gemm_desc(e, b.gc, B, Mout, b.t_out,
+                    {GemmSeg{bufB, b.c, 0, b.c, cop, b.t_out, 1, 0, 0}, GemmSeg{x, b.c_in, 0, b.c_in, cip, b.t_in, b.stride, 0, 0}}, 1, bufA, b.c);
       {
         Prof pr(e, s, PN_CONV, 2.0 * B * b.t_out * (double)(b.c + b.c_in) * b.c, 4.0 * B * b.t_out * (2.0 * b.c + b.c_in));
         ok &= launch(e, g, s->stream);
@@ -1376,20 +805,12 @@ static bool run_rnn(chiron_engine* e, Slot* s, int B) {
     // f16, whole 16-row groups filling the CUs: the projection runs inside the recurrence (lstm16f_kernel), no z
     const bool fused = e->lstm16_fused && lp.wxwide != nullptr;
     for (int pj = 0; pj < (fused ? 0 : lp.nproj); ++pj) {
-      GemmParams g;
-      init_gemm(&g, e, lp.proj[pj], B);
-      g.M = T * BP;
-      g.T_out = T;
-      g.m_time_major = 1;
-      g.nseg = 1;
       const int Kp = roundup(lp.in_w, e->kq);
-      if (l == 0)
-        g.seg[0] = GemmSeg{fea, e->C, 0, e->C, Kp, T, 1, 0, 0};
-      else if (lp.nproj == 1)
-        g.seg[0] = GemmSeg{prev, e->lasth_ld, 0, 2 * H, Kp, T, 1, 0, 1};
-      else
-        g.seg[0] = GemmSeg{prev, e->lasth_ld, e->split ? pj * roundup(H, 32) : pj * H, H, Kp, T, 1, 0, 1};
-      g.out = s->z;
+      const GemmSeg src = l == 0           ? GemmSeg{fea, e->C, 0, e->C, Kp, T, 1, 0, 0}
+                          : lp.nproj == 1 ? GemmSeg{prev, e->lasth_ld, 0, 2 * H, Kp, T, 1, 0, 1}
+                                          : GemmSeg{prev, e->lasth_ld, e->split ? pj * roundup(H, 32) : pj * H, H, Kp, T, 1, 0, 1};
+      GemmParams g = gemm_desc(e, lp.proj[pj], B, (long)T * BP, T, {src}, 0, s->z, 0);
+      g.m_time_major = 1;
       g.out_mode = 1;
       g.z_cols = zc;
       g.z_ndir = lp.nproj == 1 ? 2 : 1;
@@ -1574,6 +995,17 @@ static chiron_status submit_impl(chiron_engine* e, int32_t slot, const float* x,
                                  const int64_t* piece_row_stride, int32_t n_pieces, const int32_t* seq_len, int32_t batch, int32_t beam_width,
                                  uint32_t flags);
 
+// A host batch onto the slot's stream through its pinned staging buffers: B windows x (null: h_sig already holds them) and their
+// lengths; the padded rows of seq read 0
+static chiron_status stage_input(chiron_engine* e, Slot* s, const float* x, const int32_t* seq_len, int B) {
+  HIP_TRY(hipMemsetAsync(s->seq, 0, e->BP * 4, s->stream));
+  if (x) memcpy(s->h_sig, x, (size_t)B * e->L * 4);
+  memcpy(s->h_seq, seq_len, (size_t)B * 4);
+  HIP_TRY(hipMemcpyAsync(s->sig, s->h_sig, (size_t)B * e->L * 4, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->seq, s->h_seq, (size_t)B * 4, hipMemcpyHostToDevice, s->stream));
+  return CHIRON_OK;
+}
+
 extern "C" chiron_status chiron_engine_submit(chiron_engine* e, int32_t slot, const float* x, const int32_t* seq_len,
                                               int32_t batch, int32_t beam_width, uint32_t flags) {
   if (!x) return fail(CHIRON_ERR_INVALID, "null x/seq_len");
@@ -1614,14 +1046,12 @@ static chiron_status submit_impl(chiron_engine* e, int32_t slot, const float* x,
   // copy that is still running; the slot stays idle.
   auto enqueue = [&]() -> chiron_status {
     const float* sig;
-    HIP_TRY(hipMemsetAsync(s->seq, 0, e->BP * 4, s->stream));
     if (flags & CHIRON_X_ON_DEVICE) {
       sig = x;
+      HIP_TRY(hipMemsetAsync(s->seq, 0, e->BP * 4, s->stream));
       HIP_TRY(hipMemcpyAsync(s->seq, seq_len, (size_t)B * 4, hipMemcpyDeviceToDevice, s->stream));
     } else {
-      if (x) {
-        memcpy(s->h_sig, x, (size_t)B * e->L * 4);
-      } else {   // cross-read packing (chiron_eval.py:321-334) straight into the staging buffer: the batch is never assembled anywhere else
+      if (!x) {   // cross-read packing (chiron_eval.py:321-334) straight into the staging buffer: the batch is never assembled anywhere else
         size_t row = 0;
         for (int i = 0; i < n_pieces; ++i) {
           const int64_t stride = piece_row_stride ? piece_row_stride[i] : e->L;
@@ -1633,9 +1063,8 @@ static chiron_status submit_impl(chiron_engine* e, int32_t slot, const float* x,
           row += piece_rows[i];
         }
       }
-      memcpy(s->h_seq, seq_len, (size_t)B * 4);
-      HIP_TRY(hipMemcpyAsync(s->sig, s->h_sig, (size_t)B * e->L * 4, hipMemcpyHostToDevice, s->stream));
-      HIP_TRY(hipMemcpyAsync(s->seq, s->h_seq, (size_t)B * 4, hipMemcpyHostToDevice, s->stream));
+      const chiron_status st = stage_input(e, s, x, seq_len, B);
+      if (st) return st;
       sig = s->sig;
     }
     if (!run_cnn(e, s, B, sig) || !run_rnn(e, s, B))
@@ -1937,11 +1366,8 @@ extern "C" chiron_status chiron_engine_calibrate(chiron_engine* e, const float* 
     ctx.skipped = 0;
     auto run = [&]() -> chiron_status {
       HIP_TRY(hipMemsetAsync(ctx.dev_sums, 0, ctx.max_records * 256 * sizeof(double), s->stream));
-      HIP_TRY(hipMemsetAsync(s->seq, 0, e->BP * 4, s->stream));
-      memcpy(s->h_sig, x, (size_t)B * e->L * 4);
-      memcpy(s->h_seq, seq_len, (size_t)B * 4);
-      HIP_TRY(hipMemcpyAsync(s->sig, s->h_sig, (size_t)B * e->L * 4, hipMemcpyHostToDevice, s->stream));
-      HIP_TRY(hipMemcpyAsync(s->seq, s->h_seq, (size_t)B * 4, hipMemcpyHostToDevice, s->stream));
+      const chiron_status staged = stage_input(e, s, x, seq_len, B);
+      if (staged) return staged;
       e->calib = &ctx;
       const bool ok = run_cnn(e, s, B, s->sig) && run_rnn(e, s, B);
       e->calib = nullptr;

@@ -6,13 +6,13 @@ every product is accumulated in and every wide value is held in: float64 is the 
 realisation of the same formula).  `draw` (a numpy Generator) permutes the channels of every K dimension, another float32
 realisation of the same sums (tools/f16_ref_accuracy.py).
 
-Rounding sites, read from chiron_amd/csrc (engine.hip plan_stem_and_blocks / plan_lstm_layer / run_cnn / run_rnn and the kernels they
-launch), not from the documents:
+Rounding sites, read from chiron_amd/csrc (weight_pack.h WeightPacker::stem_and_blocks / lstm_layer, engine.hip run_cnn / run_rnn and the kernels
+they launch), not from the documents:
 
-  folding     BN folds in fp32: inv = (1 / sqrtf(var + 1e-5f)) * scale, sh = offset - mean * inv, W' = W * inv (fold_bn).  Shifts stay
+  folding     BN folds in fp32: inv = (1 / sqrtf(var + 1e-5f)) * scale, sh = offset - mean * inv, W' = W * inv (weight_pack.h fold_bn / fold_filter).  Shifts stay
               fp32; where two sites share one accumulator their shifts are added in fp32 (sh2c + sh1).  forget_bias is added to the
               LSTM bias in fp32.
-  weights     every GEMM operand is f16(W') (upload_gemm); fp16-w2 stores hi = f16(W'), lo = f16(W' - hi) and multiplies by both,
+  weights     every GEMM operand is f16(W') (WeightPacker::gemm); fp16-w2 stores hi = f16(W'), lo = f16(W' - hi) and multiplies by both,
               so the weight is hi + lo.  NOT rounded: the stem's filter (launch_stem_conv reads fp32), and the first block's
               lift_a / lift_b (conv2a of the one-channel signal) and res_a (its branch1), which are fp32 epilogue / loader operands.
   block 1     (one-channel input)  table form (default, pwl.hip): conv2a's activation is never stored and conv2b's filter never
@@ -48,7 +48,7 @@ def ident(a):
 
 
 def hilo(a32):
-    """(hi, lo) halves of a float32 array as upload_gemm forms them: hi = f16(v), lo = f16(v - float(hi)), the difference in fp32"""
+    """(hi, lo) halves of a float32 array as weight_pack.h split_half forms them: hi = f16(v), lo = f16(v - float(hi)), the difference in fp32"""
     a32 = np.asarray(a32, dtype=np.float32)
     hi = a32.astype(np.float16)
     lo = (a32 - hi.astype(np.float32)).astype(np.float16)
@@ -183,7 +183,7 @@ def lstm_direction(x, seq_len, kernel, bias, reverse, acc, draw, wq, z16, hq, oq
         wh = wh.copy()
         wh[:, col] = wh[:, col + 1]
     b32 = np.asarray(bias, dtype=fold).copy()
-    b32[2 * H:3 * H] += fold(nn_oracle.FORGET_BIAS)          # folded into the projection's shift in fp32 (plan_lstm_layer)
+    b32[2 * H:3 * H] += fold(nn_oracle.FORGET_BIAS)          # folded into the projection's shift in fp32 (WeightPacker::lstm_layer)
     zx = _mm(np.asarray(x, dtype=acc), wx, draw) + b32.astype(acc)
     if z16:
         zx = f16(zx)

@@ -58,7 +58,7 @@ def test_the_roundings_are_where_the_docstring_says():
 
 def test_hi_plus_lo_halves_reproduce_a_weight_to_2_to_the_minus_22():
     """hi + lo is W to 2^-22 relative wherever halves can hold it: from |W| = 2^-3 on.  Below, lo = f16(W - hi) is a SUBNORMAL half
-    (|W - hi| <= 2^-15 < 2^-14) with the fixed quantum 2^-24, so the error is 2^-25 absolute -- upload_gemm's fp16-w2 branch has no
+    (|W - hi| <= 2^-15 < 2^-14) with the fixed quantum 2^-24, so the error is 2^-25 absolute -- WeightPacker::gemm's fp16-w2 branch has no
     row scaling (the fp32-split branch has) -- which is what the reference reproduces."""
     rng = np.random.default_rng(3)
     spec = fc.specs()["dna"]

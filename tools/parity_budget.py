@@ -91,7 +91,7 @@ F32 = np.float32
 #   folded   BN folded into the filters (what the engine and any inference runtime does), BLAS chains
 #   chain    folded, ONE sequential fmaf chain over the whole K starting from the shift: what an MFMA accumulator (or a plain loop) does
 def fold(w, site):
-    """engine.hip:fold_bn in float32: inv = (1/sqrt(var + eps))*scale, shift = offset - mean*inv"""
+    """weight_pack.h:fold_bn in float32: inv = (1/sqrt(var + eps))*scale, shift = offset - mean*inv"""
     sc, of, mu, var = [w[site + "_bn/" + k].astype(F32) for k in ("scale", "offset", "pop_mean", "pop_var")]
     inv = ((F32(1.0) / np.sqrt(var + F32(nn_oracle.BN_EPS))).astype(F32) * sc).astype(F32)
     return inv, (of - (mu * inv).astype(F32)).astype(F32)
@@ -105,7 +105,7 @@ def fma32(a, b, c):
 
 def conv_chain(x, wf, shift, stride):
     """ONE sequential fmaf chain per output over K = taps x channels, accumulator initialised with the shift (gemm.hip: the shift is
-    the C operand of a tile's first MFMA; K order = tap-major, channels ascending, as upload_gemm lays Wt out)"""
+    the C operand of a tile's first MFMA; K order = tap-major, channels ascending, as weight_pack.h fold_filter lays Wt out)"""
     B, W, cin = x.shape
     k, _, cout = wf.shape
     out, left, right = nn_oracle.same_padding(W, k, stride)

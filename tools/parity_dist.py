@@ -10,7 +10,7 @@ distribution itself:
 
   realise   (CPU: numpy + torch's CPU sgemm -- no GPU, no product code on the arithmetic path)  For every case = topology x weight set, R
             float32 REALISATIONS of the same formulas (cnn.py:234-262, rnn.py:44-97) on N windows.  A realisation draws, per
-            convolution: BN applied to the rounded sum or folded into the filters (engine.hip:fold_bn), a random permutation of the
+            convolution: BN applied to the rounded sum or folded into the filters (weight_pack.h:fold_bn), a random permutation of the
             K = taps x channels accumulation order, a random K-blocking (32 .. K; block partials by BLAS, the blocks accumulated
             in float32 one after the other), the shift as the accumulator's start or added last; per LSTM direction: hoisted
             x-projection (bias inside / outside) or TF's concatenated [x, h] @ kernel, permuted / blocked K again, and one of two
@@ -147,7 +147,7 @@ def conv_f32(x, w, site, stride, bn, relu, rng):
         if rng.rand() < 0.5:                                   # natural: BN applied to the rounded sum (tf.nn.batch_normalization)
             y = matmul_f32(cols, wt, rng)
             y = (y * inv).astype(F32) + shift
-        else:                                                  # folded into the filters (any inference runtime; engine.hip:fold_bn)
+        else:                                                  # folded into the filters (any inference runtime; weight_pack.h:fold_bn)
             wf = (wt * inv[None, :]).astype(F32)
             if rng.rand() < 0.5:
                 y = matmul_f32(cols, wf, rng, acc0=shift)      # the shift is where the accumulator starts
