@@ -19,7 +19,8 @@
 //   cg_dw_kernel     dW_tap = X_tap^T dY on the same tiles, reduction over the rows split into slices, one partial per slice,
 //                    cg_reduce_kernel sums them in slice order.
 //   cg_rank1_*       convolutions with one input channel: forward on the VALU, weight gradient a row reduction of x * dy.
-//   cg_sum_kernel / cg_bn_bwd_sum_kernel   per-channel row reductions (moments; sum dy and sum dy * xhat with the ReLU mask fused).
+//   cg_sum_kernel / cg_bn_bwd_sum_kernel   per-channel row reductions (moments; sum dy, sum dy * xhat and sum xhat with the ReLU
+//                    mask fused).
 //   cg_bn_apply_kernel / cg_bn_bwd_apply_kernel   BN + residual add + ReLU forward; ReLU mask + BN backward.
 // Every reduction over rows goes through per-slice partials whose slice count depends on the shape alone and a second pass in
 // slice order: no float atomics, the same bits run to run.
@@ -357,7 +358,10 @@ __device__ __forceinline__ float4 cg_xhat(float4 y, float4 mu, float4 is) {
   return make_float4((y.x - mu.x) * is.x, (y.y - mu.y) * is.y, (y.z - mu.z) * is.z, (y.w - mu.w) * is.w);
 }
 
-// part[slice][0][c] = sum dy, part[slice][1][c] = sum dy * xhat, dy = din where relu_out > 0 (relu_out == nullptr: dy = din)
+// part[slice][0][c] = sum dy, part[slice][1][c] = sum dy * xhat, part[slice][2][c] = sum xhat, dy = din where relu_out > 0
+// (relu_out == nullptr: dy = din).  xhat is recomputed with the tape's float32 mean, so it is centred only up to that mean's
+// rounding; the backward's formula assumes sum xhat = 0, and where the site's input has a large mean (the raw signal) the residue is
+// amplified a hundredfold in dW.  The third sum measures it, and cg_bn_bwd_finish_kernel / cg_bn_bwd_apply_kernel take it out.
 __global__ __launch_bounds__(CG_RED_THREADS) void cg_bn_bwd_sum_kernel(const float* din, const float* relu_out, const float* y, const float* stat,
                                                                        long rows, int C, long chunk, float* part) {
   __shared__ float4 sh[CG_RED_THREADS];
@@ -365,7 +369,7 @@ __global__ __launch_bounds__(CG_RED_THREADS) void cg_bn_bwd_sum_kernel(const flo
   const int tid = threadIdx.x, c4 = tid % cl, rl = tid / cl;
   const long m0 = (long)blockIdx.x * chunk;
   const long m1 = m0 + chunk < rows ? m0 + chunk : rows;
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1, s3 = s1;
   if (rl < nrl) {
     const float4 mu = reinterpret_cast<const float4*>(stat)[c4], is = reinterpret_cast<const float4*>(stat + C)[c4];
 #pragma unroll 4
@@ -375,36 +379,43 @@ __global__ __launch_bounds__(CG_RED_THREADS) void cg_bn_bwd_sum_kernel(const flo
       const float4 xh = cg_xhat(reinterpret_cast<const float4*>(y + m * C)[c4], mu, is);
       s1 = cg_add4(s1, d);
       s2 = cg_add4(s2, make_float4(d.x * xh.x, d.y * xh.y, d.z * xh.z, d.w * xh.w));
+      s3 = cg_add4(s3, xh);
     }
   }
-  cg_block_sum(s1, sh, cl, nrl, part + (long)blockIdx.x * 2 * C);
-  cg_block_sum(s2, sh, cl, nrl, part + (long)blockIdx.x * 2 * C + C);
+  cg_block_sum(s1, sh, cl, nrl, part + (long)blockIdx.x * 3 * C);
+  cg_block_sum(s2, sh, cl, nrl, part + (long)blockIdx.x * 3 * C + C);
+  cg_block_sum(s3, sh, cl, nrl, part + (long)blockIdx.x * 3 * C + 2 * C);
 }
 
-// sums[0][c] = sum dy -> d offset; sums[1][c] = sum dy * xhat -> d scale; the statistics' slots get exactly 0
-__global__ __launch_bounds__(256) void cg_bn_bwd_finish_kernel(const float* part, int nslices, int C, float* sums, float* dbn) {
+// sum dy -> d offset; sum dy * (xhat - mean xhat) -> d scale; the statistics' slots get exactly 0.
+// sums[0][c] = mean dy, sums[1][c] = mean dy * (xhat - mean xhat), sums[2][c] = mean xhat
+__global__ __launch_bounds__(256) void cg_bn_bwd_finish_kernel(const float* part, int nslices, int C, float n, float* sums, float* dbn) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  float s1 = part[c], s2 = part[C + c];
+  float s1 = part[c], s2 = part[C + c], s3 = part[2 * C + c];
   for (int z = 1; z < nslices; ++z) {
-    s1 += part[(long)z * 2 * C + c];
-    s2 += part[(long)z * 2 * C + C + c];
+    s1 += part[(long)z * 3 * C + c];
+    s2 += part[(long)z * 3 * C + C + c];
+    s3 += part[(long)z * 3 * C + 2 * C + c];
   }
-  sums[c] = s1;
-  sums[C + c] = s2;
+  const float m3 = s3 / n;
+  s2 -= m3 * s1;
+  sums[c] = s1 / n;
+  sums[C + c] = s2 / n;
+  sums[2 * C + c] = m3;
   dbn[c] = s2;
   dbn[C + c] = s1;
   dbn[2 * C + c] = 0.f;
   dbn[3 * C + c] = 0.f;
 }
 
-// dy_out = scale * invstd * (dy - mean(dy) - xhat * mean(dy * xhat)); g_out (optional) = dy, the masked incoming gradient
+// dy_out = scale * invstd * (dy - mean(dy) - xhat * mean(dy * xhat)), xhat centred by its measured mean; g_out (optional) = dy, the
+// masked incoming gradient
 struct CgBnBwd {
   const float* din; const float* relu_out; const float* y; const float* stat; const float* scale; const float* sums;
   float* dy_out; float* g_out;
   long n4;
   int C;
-  float inv_n;
 };
 
 __global__ __launch_bounds__(256) void cg_bn_bwd_apply_kernel(const CgBnBwd p) {
@@ -414,14 +425,16 @@ __global__ __launch_bounds__(256) void cg_bn_bwd_apply_kernel(const CgBnBwd p) {
     float4 d = reinterpret_cast<const float4*>(p.din)[idx];
     if (p.relu_out) d = cg_masked(d, reinterpret_cast<const float4*>(p.relu_out)[idx]);
     const float4 mu = reinterpret_cast<const float4*>(p.stat)[c4], is = reinterpret_cast<const float4*>(p.stat + p.C)[c4];
-    const float4 xh = cg_xhat(reinterpret_cast<const float4*>(p.y)[idx], mu, is);
+    float4 xh = cg_xhat(reinterpret_cast<const float4*>(p.y)[idx], mu, is);
     const float4 sc = reinterpret_cast<const float4*>(p.scale)[c4];
     const float4 a = reinterpret_cast<const float4*>(p.sums)[c4], b = reinterpret_cast<const float4*>(p.sums + p.C)[c4];
+    const float4 m3 = reinterpret_cast<const float4*>(p.sums + 2 * p.C)[c4];
+    xh = make_float4(xh.x - m3.x, xh.y - m3.y, xh.z - m3.z, xh.w - m3.w);
     float4 o;
-    o.x = sc.x * is.x * (d.x - a.x * p.inv_n - xh.x * (b.x * p.inv_n));
-    o.y = sc.y * is.y * (d.y - a.y * p.inv_n - xh.y * (b.y * p.inv_n));
-    o.z = sc.z * is.z * (d.z - a.z * p.inv_n - xh.z * (b.z * p.inv_n));
-    o.w = sc.w * is.w * (d.w - a.w * p.inv_n - xh.w * (b.w * p.inv_n));
+    o.x = sc.x * is.x * (d.x - a.x - xh.x * b.x);
+    o.y = sc.y * is.y * (d.y - a.y - xh.y * b.y);
+    o.z = sc.z * is.z * (d.z - a.z - xh.z * b.z);
+    o.w = sc.w * is.w * (d.w - a.w - xh.w * b.w);
     if (p.g_out) reinterpret_cast<float4*>(p.g_out)[idx] = d;
     reinterpret_cast<float4*>(p.dy_out)[idx] = o;
   }
@@ -566,13 +579,13 @@ static chiron_status cg_layout(const chiron_model_desc* d, int64_t batch, int64_
   size_t part = 0;
   for (int i = 0; i < ns; ++i) {
     const CgSite& s = L.s[i];
-    size_t p = (size_t)cg_slices(s.rows).n * 2 * s.co;
+    size_t p = (size_t)cg_slices(s.rows).n * 3 * s.co;
     if (p > part) part = p;
     p = s.ci == 1 ? (size_t)cg_slices(s.rows).n * CG_R1_TAPS * s.co : (size_t)s.k * cg_nsplit(s.rows) * s.ci * s.co;
     if (p > part) part = p;
   }
   L.part = f; f += part;
-  L.sums = f; f += 2 * (size_t)(4 * CG_RED_THREADS);
+  L.sums = f; f += 3 * (size_t)(4 * CG_RED_THREADS);
   L.ws_floats = f;
   return CHIRON_OK;
 }
@@ -657,13 +670,12 @@ static void cg_bn_backward(const CgSite& s, const float* din, const float* relu_
   const long chunk = sl.chunk;
   const float* stat = tape + s.stat;
   hipLaunchKernelGGL(cg_bn_bwd_sum_kernel, dim3(nsl), dim3(CG_RED_THREADS), 0, stream, din, relu_out, tape + s.y, stat, s.rows, s.co, chunk, part);
-  hipLaunchKernelGGL(cg_bn_bwd_finish_kernel, dim3((s.co + 255) / 256), dim3(256), 0, stream, part, nsl, s.co, sums, dparams + s.bn_off);
+  hipLaunchKernelGGL(cg_bn_bwd_finish_kernel, dim3((s.co + 255) / 256), dim3(256), 0, stream, part, nsl, s.co, (float)s.rows, sums, dparams + s.bn_off);
   CgBnBwd p = {};
   p.din = din; p.relu_out = relu_out; p.y = tape + s.y; p.stat = stat; p.scale = params + s.bn_off; p.sums = sums;
   p.dy_out = dy_out; p.g_out = g_out;
   p.n4 = s.rows * (s.co / 4);
   p.C = s.co;
-  p.inv_n = 1.0f / (float)s.rows;
   hipLaunchKernelGGL(cg_bn_bwd_apply_kernel, dim3(cg_grid(p.n4, 256)), dim3(256), 0, stream, p);
 }
 

@@ -162,6 +162,52 @@ CAP_FWD_FACTOR = 4.0
 CAP_GRAD_FACTOR = 4.4321
 
 
+# Window geometry: every left pad of TF 'SAME' at every strided site, and windows of 1 to 3 frames.  left = pad_total // 2 depends on
+# L mod stride, and GRAD_CASES above reach one residue per topology (120 and 500 are multiples of 5; 120 and 150 are 1 and 3 mod 7).
+# B keeps about a hundred rows or more at every site: with a handful of rows one rounding flip is the whole of e32 (tests/f16_cases.py
+# records the same lesson).  tests/test_cnn_train_cpu.py pins what these rows reach.
+#   rna         conv2b of block 1 (k 13, stride 5): L = 121 .. 124 are residues 1 .. 4, left pads 6, 5, 5, 4; T = 25, so 225 rows at the
+#               strided sites: one whole and one partial 128-row tile, window borders inside both
+#   rna_model2  stem (k 9, stride 5): left pads 4, 3, 3, 2
+#   rna_model3  stem (k 14, stride 7): residues 2, 4, 5, 6, 0; with 120 and 150 above, every residue
+#   short       windows shorter than the strided kernel (L < k, most taps in the padding), T = 1 and 2
+#   dna         T = 1, 2, 3 and 33 at stride 1: at T = 1 both outer taps of every k = 3 convolution lie in the padding
+GEOMETRY_GRAD_CASES = ([("rna", 9, L) for L in (121, 122, 123, 124)] + [("rna_model2", 9, L) for L in (121, 122, 123, 124)] +
+                       [("rna_model3", 9, L) for L in (121, 123, 124, 125, 126)] +
+                       [("rna", 101, 3), ("rna", 40, 7), ("rna_model2", 101, 4), ("rna_model3", 60, 8)] +
+                       [("dna", 101, 1), ("dna", 48, 2), ("dna", 33, 3), ("dna", 5, 33)])
+# the factors of the bar for these cases, by the rule of the cap cases: the float32 ensemble over exactly these cases, run on the CPU
+# before any HIP result (tools/cnn_grad_accuracy.py --cases geometry -> "factor_geometry" of profiles/cnn_grad_accuracy.json): the
+# forward's largest max / median is 1.548 (dna B 101 L 1), the gradients' 4.421 (dna B 33 L 3)
+GEOMETRY_FWD_FACTOR = 4.0
+GEOMETRY_GRAD_FACTOR = 6.6315
+
+
+def site_strides(spec):
+    """[(site, k, stride)] of every convolution site, in the order of spec._sites(): the stem and a block's branch1 and conv2b carry
+    a stride, conv2a and conv2c run at stride 1."""
+    out = []
+    for site, (_, k, _, _), _ in spec._sites():
+        leaf = site.split("/")[-1]
+        if leaf in ("conv2a", "conv2c"):
+            out.append((site, k, 1))
+        else:
+            out.append((site, k, spec.stem["stride"] if site == spec.STEM_SITE
+                        else next(b["stride"] for b in spec.blocks if site.startswith(b["name"] + "/"))))
+    return out
+
+
+def site_windows(spec, L):
+    """[(site, k, stride, frames the site reads per window)], the same walk as site_rows."""
+    out, t = [], L
+    for site, k, stride in site_strides(spec):
+        out.append((site, k, stride, t))
+        leaf = site.split("/")[-1]
+        if leaf == "conv2b" or site == spec.STEM_SITE:
+            t = -(-t // stride)
+    return out
+
+
 def site_rows(spec, B, L):
     """[(site, ci, k, rows)]: the rows = B * output frames of every convolution site, the 'SAME' walk of csrc/model_layout.h restated:
     both branches of a block read the block's input, branch1 and conv2b carry its stride, conv2c runs at its output length."""

@@ -172,6 +172,130 @@ def test_cap_factors_are_the_ensemble_tools():
         assert abs(factor - prof["factor_cap"][part]) <= 5e-5 and factor >= 4.0, (part, factor, prof["factor_cap"][part])
 
 
+# ---------------------------------------------------------------------------------------------
+# the window-geometry cases: what they reach, their factors, and that the bar can tell a wrong pad
+# ---------------------------------------------------------------------------------------------
+def test_geometry_cases_reach_every_left_pad_of_every_strided_site():
+    """GEOMETRY_GRAD_CASES with GRAD_CASES run every L mod stride, hence every left pad TF 'SAME' can give, at every strided site
+    with a kernel wider than 1 of every topology.  A new topology without such cases fails here."""
+    reached = {}
+    for kind, _, L in cc.GRAD_CASES + cc.GEOMETRY_GRAD_CASES:
+        for site, k, stride, tin in cc.site_windows(cc.spec_of(kind), L):
+            if stride > 1:
+                reached.setdefault((kind, site, k, stride), set()).add(tin % stride)
+    strided = {kind: [(site, k, stride) for site, k, stride in cc.site_strides(cc.spec_of(kind)) if stride > 1] for kind in cc.SPECS}
+    assert {kind: len(v) for kind, v in strided.items()} == {"dna": 0, "rna": 2, "rna_model2": 1, "rna_model3": 1}
+    for kind, sites in strided.items():
+        for site, k, stride in sites:
+            assert reached[(kind, site, k, stride)] == set(range(stride)), (kind, site, sorted(reached[(kind, site, k, stride)]))
+    # the left pads themselves, from same_padding at a length of each residue that is no shorter than the kernel
+    lefts = {(kind, k, stride): [cnn_ref.same_padding(10 * stride + r, k, stride)[1] for r in range(stride)]
+             for kind, sites in strided.items() for _, k, stride in sites if k > 1}
+    assert lefts == {("rna", 13, 5): [4, 6, 5, 5, 4], ("rna_model2", 9, 5): [2, 4, 3, 3, 2], ("rna_model3", 14, 7): [3, 6, 6, 5, 5, 4, 4]}
+    # and what GRAD_CASES alone reach: one pad at rna and rna_model2, two of seven residues at rna_model3
+    alone = {}
+    for kind, _, L in cc.GRAD_CASES:
+        for site, k, stride, tin in cc.site_windows(cc.spec_of(kind), L):
+            if stride > 1 and k > 1:
+                alone.setdefault(kind, set()).add(tin % stride)
+    assert alone == {"rna": {0}, "rna_model2": {0}, "rna_model3": {1, 3}}
+
+
+def test_geometry_cases_reach_tiny_windows():
+    """Windows of 1, 2 and 3 frames occur, at T = 1 with a k = 3 convolution whose outer taps both lie in the padding, and every strided
+    kernel wider than 1 runs on a window shorter than itself."""
+    frames = {cc.spec_of(kind).output_len(L) for kind, _, L in cc.GEOMETRY_GRAD_CASES}
+    assert {1, 2, 3} <= frames
+    short, one_frame_k3, all_wide = set(), set(), set()
+    for kind in cc.SPECS:
+        all_wide |= {(kind, k) for _, k, stride in cc.site_strides(cc.spec_of(kind)) if stride > 1 and k > 1}
+    for kind, B, L in cc.GEOMETRY_GRAD_CASES:
+        for site, k, stride, tin in cc.site_windows(cc.spec_of(kind), L):
+            if stride > 1 and 1 < k and tin < k:
+                short.add((kind, k))
+            if k == 3 and tin == 1:
+                one_frame_k3.add(kind)
+    assert short == all_wide == {("rna", 13), ("rna_model2", 9), ("rna_model3", 14)}
+    assert {"dna", "rna", "rna_model2"} <= one_frame_k3
+    # about a hundred rows or more at every site (40 windows of 2 frames are the fewest)
+    for kind, B, L in cc.GEOMETRY_GRAD_CASES:
+        assert min(rows for _, _, _, rows in cc.site_rows(cc.spec_of(kind), B, L)) >= 80, (kind, B, L)
+    assert len(cc.GEOMETRY_GRAD_CASES) == len(set(cc.GEOMETRY_GRAD_CASES)) == 21 and not set(cc.GEOMETRY_GRAD_CASES) & set(cc.GRAD_CASES)
+
+
+def test_geometry_factors_are_the_ensemble_tools():
+    """As test_cap_factors_are_the_ensemble_tools, for "factor_geometry" over exactly GEOMETRY_GRAD_CASES; the JSON keeps one row per
+    case and part, the tensor with the largest ratio."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    prof = json.load(open(os.path.join(root, "profiles", "cnn_grad_accuracy.json")))
+    assert sorted(prof["geometry"]["cases"]) == sorted("%s B%d L%d" % c for c in cc.GEOMETRY_GRAD_CASES)
+    for part, factor in (("forward", cc.GEOMETRY_FWD_FACTOR), ("gradients", cc.GEOMETRY_GRAD_FACTOR)):
+        largest = max(case[part]["max_over_median"] for case in prof["geometry"]["cases"].values())
+        assert prof["geometry"]["largest_max_over_median"][part] == largest
+        assert prof["factor_geometry"][part] == max(4.0, 1.5 * largest)
+        assert abs(factor - prof["factor_geometry"][part]) <= 5e-5 and factor >= 4.0, (part, factor, prof["factor_geometry"][part])
+
+
+_GEOMETRY_REF = {}
+
+
+def _geometry_ref(case):
+    """The float64 and float32 restatements of one geometry case, computed once and shared (read only): forward, and gradients under
+    the signs of the float64 pre-activations; the float32 run's own free-ReLU pre-activations besides."""
+    if case not in _GEOMETRY_REF:
+        import torch
+        spec, w, x, g = cc.grad_case(*case)
+        pre64, pre32 = {}, {}
+        cnn_ref.gradients(x, spec, w, g, torch.float64, pre=pre64)
+        cnn_ref.gradients(x, spec, w, g, torch.float32, pre=pre32)
+        masks = {k: v > 0 for k, v in pre64.items()}
+        _, g64 = cnn_ref.gradients(x, spec, w, g, torch.float64, masks=masks)
+        _, g32 = cnn_ref.gradients(x, spec, w, g, torch.float32, masks=masks)
+        _GEOMETRY_REF[case] = {"fwd64": cnn_ref.forward(x, spec, w, torch.float64), "fwd32": cnn_ref.forward(x, spec, w, torch.float32),
+                               "pre64": pre64, "pre32": pre32, "masks": masks, "g64": g64, "g32": g32}
+    return _GEOMETRY_REF[case]
+
+
+@pytest.mark.parametrize("case", cc.GEOMETRY_GRAD_CASES, ids=lambda c: "%s-B%d-L%d" % c)
+def test_geometry_float32_masks_stay_within_the_mask_cap(case):
+    """The float32 restatement's own ReLU masks differ from the float64 signs within FLIP_TOL and FLIP_SHARE on these inputs (far
+    within: shares of the order of 1e-5, |pre| / rms of 1e-7), so a HIP failure of assert_masks_legitimate here is a finding."""
+    ref = _geometry_ref(case)
+    cc.assert_masks_legitimate({k: v > 0 for k, v in ref["pre32"].items()}, ref["pre64"], "%s B=%d L=%d float32" % case)
+
+
+@pytest.mark.parametrize("case", cc.GEOMETRY_GRAD_CASES, ids=lambda c: "%s-B%d-L%d" % c)
+def test_geometry_bar_rejects_a_pad_moved_by_one(case, monkeypatch):
+    """Power of the bar at these shapes: the float64 restatement with every site's padding moved one to the left (left + 1,
+    right - 1, wherever right >= 1) is NOT within GEOMETRY_*_FACTOR x e32 + FLOOR of the true one: not in the features, and in
+    the gradients (under the same fixed masks) in all tensors but at most one.  (The last block's conv2c_bn/offset gradient is the sum
+    of the masked dfeatures, whatever the convolutions do.)"""
+    import torch
+    ref = _geometry_ref(case)
+    spec, w, x, g = cc.grad_case(*case)
+    true_padding = cnn_ref.same_padding
+
+    def moved(width, k, stride):
+        out, left, right = true_padding(width, k, stride)
+        return (out, left + 1, right - 1) if right >= 1 else (out, left, right)
+    monkeypatch.setattr(cnn_ref, "same_padding", moved)
+    f_mut, m_mut = cnn_ref.forward(x, spec, w, torch.float64)
+    _, g_mut = cnn_ref.gradients(x, spec, w, g, torch.float64, masks=ref["masks"])
+    monkeypatch.undo()
+    (f64, m64), (f32, m32) = ref["fwd64"], ref["fwd32"]
+    assert f_mut.shape == f64.shape
+    fwd = cc.row(f_mut, f64, f32, cc.GEOMETRY_FWD_FACTOR)
+    assert not fwd["ok"], ("features", fwd)
+    # the first wide site's own moments see it too (sites before it are untouched: k = 1 has no padding)
+    first = next(site for site, k, _ in cc.site_strides(spec) if k > 1)
+    seen = [cc.row(m_mut[first][i], m64[first][i], m32[first][i], cc.GEOMETRY_FWD_FACTOR)["ok"] for i in (0, 1)]
+    assert not all(seen), (first, seen)
+    rows = {name: cc.row(g_mut[name], ref["g64"][name], ref["g32"][name], cc.GEOMETRY_GRAD_FACTOR) for name in ref["g64"]}
+    passed = [name for name, r in rows.items() if r["ok"]]
+    print("%s B=%d L=%d:" % case, "%d of %d gradient tensors reject the moved pad; not: %s" % (len(rows) - len(passed), len(rows), passed))
+    assert len(passed) <= 1, passed
+
+
 @pytest.mark.parametrize("bn_mode", ["population", "batch"])
 @pytest.mark.parametrize("kind", ["dna", "rna_model3"])
 def test_init_weights_variable_set_and_distributions(kind, bn_mode):

@@ -97,6 +97,40 @@ def test_gradients_past_the_reduction_caps(built, case):
         assert flat2.tobytes() == hip["flat"].tobytes() and dfeat2.tobytes() == hip["dfeatures"].tobytes()
 
 
+@pytest.mark.parametrize("case", tc.GEOMETRY_CASES, ids=lambda c: "%s-B%d-T%d" % c)
+def test_forward_and_gradients_at_tiny_and_odd_frame_counts(built, case):
+    """T = 1, 2, 3, 17 and 33 with lengths drawn from 0 .. T (tests/train_cases.py, GEOMETRY_CASES).  The logits are held as
+    test_forward_against_the_oracle_and_the_engine holds them, every gradient and dfeatures to the bar of the cases above.  At
+    T = 1 no step has a predecessor: chiron_rnn_train_backward zeroes dWh in a branch of its own, and the recurrent rows of every
+    kernel gradient are exactly 0.  The reductions run in a fixed order: two identical calls, the same bits."""
+    from oracle import nn_oracle
+    kind, B, T = case
+    spec, w, fea, sl, dl = tc.geometry_case(kind, B, T)
+    assert tuple(sl[:3]) == (0, 1, T)
+    hip = {}
+    rows = tc.accuracy(spec, w, fea, sl, dl, hip_out=hip)
+    label = "%s B=%d T=%d" % case
+    w64 = {k: np.asarray(v, dtype=np.float64) for k, v in w.items()}
+    ref = nn_oracle.fc_head(nn_oracle.rnn_forward(fea.astype(np.float64), sl, spec.to_dict(), w64), w64)
+    assert hip["logits"].shape == ref.shape == (B, T, 5)
+    err = float(np.abs(hip["logits"].astype(np.float64) - ref).max())
+    print("%s: max |train forward - oracle| = %.3g" % (label, err))
+    assert err <= 1e-4
+    _assert_rows(rows, label)
+    assert set(rows) == set(train.param_layout(spec)) | {"dfeatures"}
+    for b in range(B):     # d features is exactly 0 past every row's end
+        assert not hip["dfeatures"][b, sl[b]:].any(), b
+    if T == 1:
+        kernels = [name for name in hip["named"] if name.endswith("lstm_cell/kernel")]
+        assert len(kernels) == 2 * spec.rnn_layers
+        for name in kernels:
+            grad = hip["named"][name]
+            in_w = grad.shape[0] - spec.hidden
+            assert grad[:in_w].any() and not grad[in_w:].any(), name
+    _, _, dfeat2, flat2, _ = tc.hip_forward_backward(spec, w, fea, sl, dl)
+    assert flat2.tobytes() == hip["flat"].tobytes() and dfeat2.tobytes() == hip["dfeatures"].tobytes()
+
+
 @pytest.mark.parametrize("name", ["write-through", "closed", "integrate-no-output", "hold-and-output", "midpoint"])
 def test_gradients_with_saturated_gates(built, name):
     spec = ca.dna_default_spec()

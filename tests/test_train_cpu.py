@@ -161,6 +161,47 @@ def test_row_slices_tile_every_row_count():
         assert head_wg <= g.head_wg_max
 
 
+# ---------------------------------------------------------------------------------------------
+# the tiny and odd frame counts
+# ---------------------------------------------------------------------------------------------
+def test_geometry_cases_reach_tiny_and_odd_frame_counts():
+    """GEOMETRY_CASES run both recurrent wirings at T = 1, 2 and 3 and at frame counts that are multiples of nothing in the kernels;
+    their lengths cover 0, 1 and T in every case, which ragged_seq_len cannot draw at T = 1."""
+    g = _RgGeometry()
+    for kind in ("dna-stack", "rna-multi"):
+        frames = sorted(T for k, _, T in tc.GEOMETRY_CASES if k == kind)
+        assert frames == [1, 2, 3, 17, 33]
+        assert sum(1 for T in frames if T > 3 and T % 2 and T % g.gk) >= 2
+    assert len(tc.GEOMETRY_CASES) == len(set(tc.GEOMETRY_CASES)) == 10
+    for kind, B, T in tc.GEOMETRY_CASES:
+        spec, w, fea, sl, dl = tc.geometry_case(kind, B, T)
+        assert fea.shape == (B, T, 256) and dl.shape == (B, T, 5) and sl.shape == (B,) and sl.dtype == np.int32
+        assert (fea >= 0).all() and 0.3 < (fea == 0).mean() < 0.7          # post-ReLU-like
+        assert tuple(sl[:3]) == (0, 1, T) and sl.min() >= 0 and sl.max() <= T
+        assert B * T >= 96                                                  # about a hundred rows or more
+        spec2, _, fea2, sl2, dl2 = tc.geometry_case(kind, B, T)           # seeded by the case alone
+        assert fea2.tobytes() == fea.tobytes() and sl2.tobytes() == sl.tobytes() and dl2.tobytes() == dl.tobytes()
+    with pytest.raises(ValueError):
+        tc.ragged_seq_len(5, 1, np.random.default_rng(0))
+    sl = tc.geometry_seq_len(2000, 3, np.random.default_rng(0))
+    assert set(sl.tolist()) == {0, 1, 2, 3}
+
+
+@pytest.mark.parametrize("kind", ["dna-stack", "rna-multi"])
+def test_reference_at_one_frame_has_no_recurrent_gradient(kind):
+    """What the GPU test asserts of the kernels at T = 1 holds of the float64 reference: no step has a predecessor, so the recurrent
+    rows of every lstm kernel's gradient are exactly 0 and the input rows are not."""
+    import torch
+    spec, w, fea, sl, dl = tc.geometry_case(kind, 101, 1)
+    _, g64, dx64 = rnn_ref.gradients(fea, sl, spec, w, dl, torch.float64)
+    kernels = [name for name in g64 if name.endswith("lstm_cell/kernel")]
+    assert len(kernels) == 2 * spec.rnn_layers
+    for name in kernels:
+        in_w = g64[name].shape[0] - spec.hidden
+        assert g64[name][:in_w].any() and not g64[name][in_w:].any(), name
+    assert not dx64[sl == 0].any() and dx64[sl == 1].any()
+
+
 def test_write_bundle_round_trip_and_crc(built, tmp_path):
     rng = np.random.default_rng(2)
     tensors = {"a/%03d/w" % i: rng.normal(size=(3, i + 1)).astype(np.float32) for i in range(90)}

@@ -30,6 +30,13 @@ def ragged_seq_len(B, T, rng):
     return sl.astype(np.int32)[:B]
 
 
+def geometry_seq_len(B, T, rng):
+    """Lengths uniform in 0 .. T with rows 0 to 2 set to (0, 1, T): what ragged_seq_len cannot draw at T = 1."""
+    sl = rng.integers(0, T + 1, size=B)
+    sl[:3] = (0, 1, T)
+    return sl.astype(np.int32)[:B]
+
+
 def oracle_features(spec, weights, B, segment_len, rng):
     """The float64 oracle's own CNN features [B, T, C] of seeded synthetic signal."""
     from oracle import nn_oracle
@@ -70,10 +77,10 @@ def rel_l2(a, ref):
 def accuracy(spec, weights, fea, seq_len, dlogits, hip_out=None):
     """Per tensor (every named parameter + 'dfeatures'): err (HIP against float64), e32 (float32 restatement against float64),
     norm of the float64 gradient, and whether the bar holds.  dlogits: array, or callable(logits tensor on the GPU) -> array / tensor.
-    hip_out: a dict that receives the HIP run's flat dparams and dfeatures."""
-    _, named, dfeat, flat, g_used = hip_forward_backward(spec, weights, fea, seq_len, dlogits)
+    hip_out: a dict that receives the HIP run's flat dparams, dfeatures, logits and named gradients."""
+    logits, named, dfeat, flat, g_used = hip_forward_backward(spec, weights, fea, seq_len, dlogits)
     if hip_out is not None:
-        hip_out.update(flat=flat, dfeatures=dfeat)
+        hip_out.update(flat=flat, dfeatures=dfeat, logits=logits, named=named)
     _, g64, dx64 = rnn_ref.gradients(fea, seq_len, spec, weights, g_used, torch.float64)
     _, g32, dx32 = rnn_ref.gradients(fea, seq_len, spec, weights, g_used, torch.float32)
     rows = {}
@@ -105,6 +112,21 @@ def cap_case(kind, B, T):
     rng = np.random.default_rng(100 + T)
     fea = random_features(B, T, 256, rng)
     sl = ragged_seq_len(B, T, rng)
+    return spec, ca.synthetic_weights(spec, seed=7), fea, sl, rng.normal(size=(B, T, 5)).astype(np.float32)
+
+
+# Tiny and odd frame counts, (kind, B, T): T = 1 (no recurrent step at all: chiron_rnn_train_backward zeroes dWh instead of running a
+# GEMM over M - BP = 0 rows), 2 and 3 frames, and T = 17 and 33, multiples of nothing in rg_lstm_fwd / rg_lstm_bwd or the 16-row k-tile.
+# B keeps about a hundred rows or more (T * B) and is off the kernels' 16-row multiple except at 48.
+GEOMETRY_CASES = [(kind, B, T) for kind in ("dna-stack", "rna-multi") for B, T in ((101, 1), (48, 2), (33, 3), (7, 17), (5, 33))]
+
+
+def geometry_case(kind, B, T):
+    """-> (spec, weights, post-ReLU-like features, seq_len, random dlogits) of one GEOMETRY_CASES entry, seeded by the case alone."""
+    spec = specs()[kind]
+    rng = np.random.default_rng(1000 * B + T)
+    fea = random_features(B, T, 256, rng)
+    sl = geometry_seq_len(B, T, rng)
     return spec, ca.synthetic_weights(spec, seed=7), fea, sl, rng.normal(size=(B, T, 5)).astype(np.float32)
 
 

@@ -10,14 +10,17 @@ float64, the median member's, and the largest member's ratio to that median.
              (max / median up to 3e4 was measured that way), which no bar of a few rounding errors can absorb.
 factor = max(4, 1.5 x the largest ratio), for the forward and for the gradients separately.
 The same ensemble over CAP_GRAD_CASES (the shapes past the caps of the row reductions) gives "factor_cap" by the same rule, kept
-apart so that the factor of the cases above stays what it was derived from; its rows are under "cap".
+apart so that the factor of the cases above stays what it was derived from; its rows are under "cap".  GEOMETRY_GRAD_CASES (every
+'SAME' left pad of the strided sites, windows of 1 to 3 frames) give "factor_geometry" in the same way; under "geometry" each of the
+21 cases keeps one row for the forward and one for the gradients: the tensor with the largest ratio.
 
 --hip (needs a GPU): the HIP path's err / e32 on the same cases, merged into the same file under "hip"; the default mode keeps an
-existing "hip" block.  The cap cases' rows go under "hip" / "cap_cases".
+existing "hip" block.  The cap cases' rows go under "hip" / "cap_cases", the geometry cases' under "hip" / "geometry_cases" (one
+row per case: the tensor with the largest err / e32 above the floor, and whether every tensor met its bar).
 
---cases grad | cap: only that list of cases; what the file holds for the other one is kept.
+--cases grad | cap | geometry: only that list of cases; what the file holds for the others is kept.
 
-    python tools/cnn_grad_accuracy.py [--draws 8] [--cases all|grad|cap] [--hip] [--out profiles/cnn_grad_accuracy.json]
+    python tools/cnn_grad_accuracy.py [--draws 8] [--cases all|grad|cap|geometry] [--hip] [--out profiles/cnn_grad_accuracy.json]
 """
 import argparse
 import json
@@ -40,8 +43,15 @@ def spread(errs, norm):
     return {"norm": norm, "plain_err": errs[0], "median_err": med, "max_err": max(errs), "max_over_median": max(errs) / med if med > 0 else 0.0}
 
 
-def ensemble(draws, case_list):
-    """-> (largest max / median of the forward and of the gradients, factors by the rule, rows per case)"""
+def widest(rows):
+    """One row for a case: the tensor with the largest max / median, with its figures."""
+    name = max(rows, key=lambda k: rows[k]["max_over_median"])
+    return dict(rows[name], tensor=name, tensors=len(rows))
+
+
+def ensemble(draws, case_list, per_case=False):
+    """-> (largest max / median of the forward and of the gradients, factors by the rule, rows per case).  per_case: one row per
+    case and part (the tensor with the largest ratio) instead of one per tensor."""
     cases, largest = {}, {"forward": 0.0, "gradients": 0.0}
     for kind, B, L in case_list:
         spec, w, x, g = cc.grad_case(kind, B, L)
@@ -59,7 +69,7 @@ def ensemble(draws, case_list):
                                                          float(np.linalg.norm(m64[site][i])))
         gradients = {name: spread([float(np.linalg.norm(m[name] - g64[name])) for m in grd], float(np.linalg.norm(g64[name]))) for name in g64}
         label = "%s B%d L%d" % (kind, B, L)
-        cases[label] = {"forward": forward, "gradients": gradients}
+        cases[label] = {"forward": widest(forward), "gradients": widest(gradients)} if per_case else {"forward": forward, "gradients": gradients}
         for part, rows in (("forward", forward), ("gradients", gradients)):
             largest[part] = max(largest[part], max(r["max_over_median"] for r in rows.values()))
         print(label, "largest max/median: forward %.3g, gradients %.3g" % (max(r["max_over_median"] for r in forward.values()),
@@ -74,8 +84,9 @@ def method(draws):
             "draws": draws}
 
 
-def hip(factor, case_list):
-    """-> (largest err / e32 above the floor, rows per case)"""
+def hip(factor, case_list, per_case=False):
+    """-> (largest err / e32 above the floor, rows per case).  per_case: one row per case (the tensor with the largest err / e32
+    above the floor, and whether every tensor met its bar) instead of one per tensor."""
     out, worst = {}, 0.0
     for kind, B, L in case_list:
         spec, w, x, g = cc.grad_case(kind, B, L)
@@ -84,7 +95,11 @@ def hip(factor, case_list):
         rows = dict(cc.forward_rows(spec, w, x, fea, mom, factor["forward"]))
         rows.update(cc.gradient_rows(spec, w, x, dp, gu, masks, factor["gradients"], label))
         out[label] = {k: {"err_over_e32": r["ratio"], "err_rel": r["err_rel"], "e32_rel": r["e32_rel"], "ok": r["ok"]} for k, r in rows.items()}
-        worst = max(worst, max(r["ratio"] for r in rows.values() if r["err_rel"] > cc.FLOOR))
+        if per_case:
+            above = {k: v for k, v in out[label].items() if v["err_rel"] > cc.FLOOR} or out[label]
+            name = max(above, key=lambda k: above[k]["err_over_e32"])
+            out[label] = dict(above[name], tensor=name, tensors=len(rows), ok=all(v["ok"] for v in out[label].values()))
+        worst = max(worst, max((r["ratio"] for r in rows.values() if r["err_rel"] > cc.FLOOR), default=0.0))
         print(label, "largest err/e32 %.3g" % max(r["ratio"] for r in rows.values()), flush=True)
     return worst, out
 
@@ -93,37 +108,56 @@ HIP_NOTE = ("chiron_cnn_train_forward / _backward against the same float64 value
             "under the HIP run's own ReLU masks; measured after the factors were fixed")
 
 
+def dump(out):
+    """indent=1 as ever, except that a case of the one-row-per-case lists takes one line."""
+    lines, flat = {}, json.loads(json.dumps(out))
+    for rows in (flat.get("geometry", {}).get("cases"), flat.get("hip", {}).get("geometry_cases")):
+        for label in rows or ():
+            key = "@@%d@@" % len(lines)
+            lines[key] = json.dumps(rows[label])
+            rows[label] = key
+    text = json.dumps(flat, indent=1)
+    for key, line in lines.items():
+        text = text.replace('"%s"' % key, line)
+    return text
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--draws", type=int, default=8)
     ap.add_argument("--hip", action="store_true")
-    ap.add_argument("--cases", choices=["all", "grad", "cap"], default="all")
+    ap.add_argument("--cases", choices=["all", "grad", "cap", "geometry"], default="all")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cnn_grad_accuracy.json"))
     a = ap.parse_args()
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     old = json.load(open(a.out)) if os.path.exists(a.out) else {}
     out = old
+    # the lists past the first: (name under --cases, its cases, key of its factors, key of its ensemble rows, prefix under "hip",
+    # one row per case instead of one per tensor)
+    extra = [("cap", cc.CAP_GRAD_CASES, "factor_cap", "cap", "cap_", False),
+             ("geometry", cc.GEOMETRY_GRAD_CASES, "factor_geometry", "geometry", "geometry_", True)]
+    chosen = [e for e in extra if a.cases in ("all", e[0])]
     if a.hip:
-        if not isinstance(old.get("factor"), dict) or (a.cases != "grad" and not isinstance(old.get("factor_cap"), dict)):
+        if (a.cases in ("all", "grad") and not isinstance(old.get("factor"), dict)) or any(not isinstance(old.get(e[2]), dict) for e in chosen):
             raise SystemExit("run the CPU ensemble first: --hip reads its factors from %s" % a.out)
         h = out.setdefault("hip", {})
         h["note"] = HIP_NOTE
-        if a.cases != "cap":
+        if a.cases in ("all", "grad"):
             h["largest_err_over_e32_above_the_floor"], h["cases"] = hip(old["factor"], cc.GRAD_CASES)
-        if a.cases != "grad":
-            h["cap_largest_err_over_e32_above_the_floor"], h["cap_cases"] = hip(old["factor_cap"], cc.CAP_GRAD_CASES)
+        for _, case_list, factor_key, _, prefix, per_case in chosen:
+            h[prefix + "largest_err_over_e32_above_the_floor"], h[prefix + "cases"] = hip(old[factor_key], case_list, per_case)
     else:
-        if a.cases != "cap":
+        if a.cases in ("all", "grad"):
             out = dict(method(a.draws))
             out["largest_max_over_median"], out["factor"], out["cases"] = ensemble(a.draws, cc.GRAD_CASES)
-            out.update({k: old[k] for k in ("factor_cap", "cap", "hip") if k in old})
+            out.update({k: old[k] for k in ("factor_cap", "cap", "factor_geometry", "geometry", "hip") if k in old})
             print("largest ratios %s -> factors %s" % (out["largest_max_over_median"], out["factor"]))
-        if a.cases != "grad":
-            largest, out["factor_cap"], rows = ensemble(a.draws, cc.CAP_GRAD_CASES)
-            out["cap"] = {"draws": a.draws, "largest_max_over_median": largest, "cases": rows}
-            print("cap cases: largest ratios %s -> factor_cap %s" % (largest, out["factor_cap"]))
+        for name, case_list, factor_key, rows_key, _, per_case in chosen:
+            largest, out[factor_key], rows = ensemble(a.draws, case_list, per_case)
+            out[rows_key] = {"draws": a.draws, "largest_max_over_median": largest, "cases": rows}
+            print("%s cases: largest ratios %s -> %s %s" % (name, largest, factor_key, out[factor_key]))
     with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
+        f.write(dump(out))
 
 
 if __name__ == "__main__":
