@@ -190,6 +190,7 @@ struct chiron_engine : NetPlans {   // T, C, the stem, blocks, lstm and the FC h
   int maxB = 0, BP = 0;
   bool stream32 = true;           // fp32: 1 x 1 convolutions on the weight-stationary streaming kernel (CHIRON_NO_STREAM32=1: gemm.hip, A/B switch)
   bool stream16 = true;           // f16: 1 x 1 convolutions on the streaming kernel (CHIRON_NO_STREAM16=1: gemm.hip, A/B switch)
+  bool proj_bf16 = true;          // fp32: the K = 256 / K = 200 LSTM x-projections as six-term bf16 products (CHIRON_PROJ_FP32=1: the fp32 MFMA kernels)
   bool dyn_tiles = true;          // DMA GEMM: tiles handed out by per-XCD counters instead of fixed shares (CHIRON_STATIC_TILES=1: off)
   int lstm16_pair = -1;           // f16 fused recurrence, two 16-row groups per workgroup: 1 always, 0 never (CHIRON_LSTM16_PAIR), -1 when single groups would not fit one round
   bool lstm16_fused = false;      // f16: x-projection inside the recurrence (whole 16-row groups that fill the CUs)
@@ -252,8 +253,23 @@ static chiron_status build_plans(chiron_engine* e, const float* w) {
   sw.split_rec32 = getenv("CHIRON_SPLIT_REC32") != nullptr;
   if (e->split) sw.split_row_scale = split_row_scale();
   std::vector<Upload> ups;
-  const chiron_status st = pack_weights(e->desc, e->map, w, e->L, e->opts.dtype, sw, e, &ups);
-  return st ? st : upload_plans(e, ups);
+  chiron_status st = pack_weights(e->desc, e->map, w, e->L, e->opts.dtype, sw, e, &ups);
+  if (st) return st;
+  // fp32 engines: the projections gemm_proj_bf16x3_kernel covers get their weights a second time, as three bf16 planes cut from the packed
+  // fp32 rows while the packer's host copy is still there
+  if (e->proj_bf16 && e->opts.dtype == CHIRON_F32 && !e->bn_batch) {
+    for (LstmPlan& lp : e->lstm) {
+      ConvGemmPlan& g = lp.proj[0];
+      if (lp.nproj != 1 || (lp.in_w != 256 && lp.in_w != 200) || g.N % BF3_BN != 0) continue;
+      for (const Upload& u : ups) {
+        if (u.dst != reinterpret_cast<void**>(&g.Wt)) continue;
+        const std::vector<uint16_t> planes = bf16x3_planes(static_cast<const float*>(u.data), g.N, g.K, lp.in_w);
+        if ((st = dev_alloc(e, &g.w_bf3, planes.size() * sizeof(uint16_t), false))) return st;
+        HIP_TRY(hipMemcpy(g.w_bf3, planes.data(), planes.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+      }
+    }
+  }
+  return upload_plans(e, ups);
 }
 
 // ---- sizes of an engine, computable without a GPU: the frame count, the largest tensor a kernel addresses with a
@@ -426,6 +442,7 @@ extern "C" chiron_status chiron_engine_create(const chiron_model_desc* desc, con
   e->lstm16_pair = getenv("CHIRON_LSTM16_PAIR") ? atoi(getenv("CHIRON_LSTM16_PAIR")) : -1;
   e->stream16 = getenv("CHIRON_NO_STREAM16") == nullptr && opts->dtype != CHIRON_F16_W2;   // (the streaming kernels hold ONE half per weight in registers)
   e->stream32 = getenv("CHIRON_NO_STREAM32") == nullptr;
+  e->proj_bf16 = getenv("CHIRON_PROJ_FP32") == nullptr;   // A/B switch, per engine: the fp32 MFMA projections
   e->dyn_tiles = getenv("CHIRON_STATIC_TILES") == nullptr;   // A/B switch: fixed tile shares per workgroup
   {
     // f16 engines run the x-projection inside the recurrence (lstm16f_kernel) from 64 sixteen-row workgroups up (B >= 512:
@@ -816,6 +833,7 @@ static bool run_rnn(chiron_engine* e, Slot* s, int B) {
       g.z_ndir = lp.nproj == 1 ? 2 : 1;
       g.z_dir0 = lp.nproj == 1 ? 0 : pj;
       g.z_seq_len = s->seq;
+      g.w_bf3 = lp.proj[pj].w_bf3;   // non-null: gemm_proj_bf16x3_kernel (build_plans)
       g.z_f16 = (e->f16 && (!e->w2 || e->w2_zf16)) ? 1 : 0;
       const double ndir = lp.nproj == 1 ? 2.0 : 1.0;
       // layer 0 reads the CNN features (K = 256: its own kernel instantiation), the other layers the recurrent output

@@ -12,6 +12,8 @@
 //   validity are computed once per segment.
 //
 //   gemm_f32_dma_kernel  every launch whose A operand is a tensor in HBM: LDS-DMA staging (see below).
+//   gemm_proj_bf16x3_kernel  the fp32 engine's LSTM x-projections of 256 / 200 channels: each fp32 product as six exact bf16 products
+//                        on v_mfma_f32_32x32x16_bf16, 6 / 16 of the fp32 matrix time (below; CHIRON_PROJ_FP32=1: gemm_f32_dma_kernel).
 //   gemm_f32_kernel      register-staged ([rows][36] LDS image, masked loads): the lifted first convolution, whose A
 //                        operand relu(sig*a[c]+b[c]) is computed in the loader, and shapes the DMA kernel is not
 //                        instantiated for.
@@ -1059,6 +1061,242 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_dma_kernel(const GemmParams p
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------
+// fp32 LSTM x-projection as six-term bf16 products.  An fp32 value is exactly hi + mid + lo, three bf16 values of 8
+// significand bits each; every product of two parts is exact in fp32, and the six products of weight 2^-8 (i + j - 2), i + j <= 4,
+// leave out only terms below 2^-24 of the product.  v_mfma_f32_32x32x16_bf16 runs at 16 x the fp32 MFMA rate: 6 / 16 of the matrix time.
+//   * same 128 x 160 tile, waves 4 x 1, XCD-aware tile ids, tiles by counter, shift as the first C operand and z epilogue as the fp32
+//     projection (the 32x32 accumulator layout is the same).
+//   * A stays fp32 in HBM and in the LDS: 16-k stages, [128 rows][16 floats] filled by LDS-DMA, the 16-byte slot s of row r at
+//     s ^ ((r >> 2) & 3).  A lane reads its two slots (k = 4 kh + j and 8 + 4 kh + j) and cuts each value into its three parts.
+//   * B comes as three bf16 planes prepared on the host in exactly the stage image the kernel reads (weight_pack.h bf16x3_planes):
+//     15 lane-linear 1 KB DMA pieces per stage, one ds_read_b128 = the eight k of one plane.
+//   * 8 + 15 KB per stage, two buffers: 50 KB with the shift table, two workgroups per CU as before.  (A third buffer with the DMA two
+//     stages ahead and a counted vmcnt measured no gain in the three-batch mix: DESIGN 3.10.)
+// ---------------------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+constexpr int BF3_TERMS = 6;            // 9: every product of two parts (9 / 16 of the fp32 matrix time)
+constexpr bool BF3_SMALL_FIRST = true;  // order of the terms of one k-step: ascending magnitude
+
+// eight fp32 values -> the A fragments of their hi / mid / lo parts (cut, not rounded: both subtractions are exact)
+__device__ __forceinline__ void bf3_split(const f32x4& x0, const f32x4& x1, bf16x8& h, bf16x8& m, bf16x8& l) {
+  unsigned hb[8], mb[8], lb[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float x = e < 4 ? x0[e] : x1[e - 4];
+    hb[e] = __builtin_bit_cast(unsigned, x);
+    const float r = x - __builtin_bit_cast(float, hb[e] & 0xffff0000u);
+    mb[e] = __builtin_bit_cast(unsigned, r);
+    lb[e] = __builtin_bit_cast(unsigned, r - __builtin_bit_cast(float, mb[e] & 0xffff0000u));
+  }
+  u32x4 hp, mp, lp;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {   // upper halves of elements 2i (low) and 2i + 1 (high): one v_perm_b32
+    hp[i] = __builtin_amdgcn_perm(hb[2 * i + 1], hb[2 * i], 0x07060302u);
+    mp[i] = __builtin_amdgcn_perm(mb[2 * i + 1], mb[2 * i], 0x07060302u);
+    lp[i] = __builtin_amdgcn_perm(lb[2 * i + 1], lb[2 * i], 0x07060302u);
+  }
+  h = __builtin_bit_cast(bf16x8, hp);
+  m = __builtin_bit_cast(bf16x8, mp);
+  l = __builtin_bit_cast(bf16x8, lp);
+}
+
+// NST 16-k stages (16: K = 256; 13: cin = 200, TAIL: the last stage holds 8 real channels)
+template <int NST, bool TAIL>
+__global__ __launch_bounds__(256, 2) void gemm_proj_bf16x3_kernel(const GemmParams p) {
+  constexpr int BN = BF3_BN, NNI = 5;
+  constexpr int A_F = GEMM_BM * BF3_BK;       // floats per A stage (8 KB)
+  constexpr int B_F = BF3_STAGE_BYTES / 4;    // 4-byte units per B stage (15 KB)
+  constexpr int B_PIECES = BF3_STAGE_BYTES / 1024;
+  __shared__ __attribute__((aligned(16))) float lds[2 * A_F + 2 * B_F + DMA_MAX_N];  // A0 A1 B0 B1 shift
+  float* const As = lds;
+  float* const Bs = As + 2 * A_F;
+  float* const shl = Bs + 2 * B_F;
+
+  const int tid = threadIdx.x;
+  if (p.K < 0) lds[tid] = 0.f;   // the tiles are only ever written by the DMA engine (see gemm_f32_dma_kernel)
+  for (int n = tid; n < DMA_MAX_N; n += 256) shl[n] = n < p.N ? p.shift[n] : 0.f;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31;
+  const int kh = lane >> 5;
+
+  const int nblocks_n = p.N / BN;   // whole tiles (launch_dma)
+  const int mblocks = (p.M + GEMM_BM - 1) / GEMM_BM;
+  const int total_ids = ((mblocks + 7) / 8) * 8 * nblocks_n;
+
+  auto tile_of = [&](int id, int& m0, int& n0) -> bool {
+    const int xcd = id & 7;
+    const int slot = id >> 3;
+    const int mblk = (slot / nblocks_n) * 8 + xcd;
+    m0 = mblk * GEMM_BM;
+    n0 = (slot % nblocks_n) * BN;
+    return mblk < mblocks;
+  };
+  auto next_valid = [&](int id) -> int {
+    int m0, n0;
+    do id += gridDim.x;
+    while (id < total_ids && !tile_of(id, m0, n0));
+    return id;
+  };
+
+  // ---- DMA geometry.  A: piece j (0, 1) of wave w covers tile rows 32 w + 16 j .. + 15, lane -> (row lane >> 2, physical slot
+  //      lane & 3); the logical slot behind it is (lane & 3) ^ ((row >> 2) & 3) = (lane & 3) ^ ((lane >> 4) & 3) for every piece.
+  //      B: piece q of the stage image is its bytes 1024 q .. + 1023, wave w takes q = w, w + 4, ...
+  const int arow = wave * 32 + (lane >> 2);                   // + 16 j
+  const int alog = ((lane & 3) ^ ((lane >> 4) & 3)) * 4;      // in floats
+  const GemmSeg& sg = p.seg[0];
+  const __amdgpu_buffer_rsrc_t ra = dma_rsrc(sg.src), rb = dma_rsrc(reinterpret_cast<const float*>(p.w_bf3));
+  const unsigned blane = (unsigned)lane * 16u;
+  unsigned aoff[2];   // byte offset of this lane's 16 bytes of stage 0, or DMA_OOB
+  unsigned btile = 0;   // byte offset of the tile's first stage image
+  auto load_tile = [&](int id) {
+    int m0, n0;
+    tile_of(id, m0, n0);
+    const RowSplit rs(m0, p.BP);
+    btile = (unsigned)(n0 / BN) * (unsigned)(NST * BF3_STAGE_BYTES);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      int t, b;
+      rs.split(arow + 16 * j, t, b);
+      const int in_t = t * sg.stride + sg.shift;
+      const bool ok = m0 + arow + 16 * j < p.M && b < p.B && in_t >= 0 && in_t < sg.w_in;
+      const long row = sg.time_major ? ((long)in_t * p.BP + b) : ((long)b * sg.w_in + in_t);
+      aoff[j] = ok ? (unsigned)((row * sg.lda + sg.col0 + alog) * 4) : DMA_OOB;
+    }
+  };
+  // stage c of the tile behind aoff / btile into buffer nb.  The stage's offset travels in the scalar offset; in the last stage of a
+  // K tail the channels >= cin must read zeros BEFORE they are split (whatever the buffer holds there times 0 may be NaN).
+  auto issue = [&](int c, int nb) {
+    float* const a_dst = As + nb * A_F + wave * 512;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (TAIL && c == NST - 1) {
+        const bool ok = aoff[j] != DMA_OOB && c * BF3_BK + alog < sg.cin;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lptr_t)(a_dst + j * 256), 16, ok ? aoff[j] + (unsigned)c * (BF3_BK * 4u) : DMA_OOB, 0, 0, 0);
+      } else {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lptr_t)(a_dst + j * 256), 16, aoff[j], c * (BF3_BK * 4), 0, 0);
+      }
+    }
+    float* const b_dst = Bs + nb * B_F;
+#pragma unroll
+    for (int j = 0; j < (B_PIECES + 3) / 4; ++j) {
+      const int q = wave + 4 * j;
+      if (q < B_PIECES)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lptr_t)(b_dst + q * 256), 16, blane, (int)btile + c * BF3_STAGE_BYTES + q * 1024, 0, 0);
+    }
+  };
+
+  // ---- tile ids: as gemm_f32_dma_kernel (same counters, same numbers taken per launch)
+  __shared__ int sh_next;
+  const bool dyn = p.tile_ctr != nullptr;
+  const int my_xcd = blockIdx.x & 7;
+  const unsigned slots_per_xcd = (unsigned)(total_ids >> 3);
+  unsigned long long grabbed = 0;
+  auto issue_grab = [&]() {
+    if (tid == 0) grabbed = atomicAdd(p.tile_ctr + my_xcd, 1ull);
+  };
+  auto decode_grab = [&]() -> int {
+    for (;;) {
+      const unsigned long long v = grabbed - p.tile_base;
+      if (v >= slots_per_xcd) return total_ids;
+      const int id = (int)((unsigned)v << 3) | my_xcd;
+      int mm, nn;
+      if (tile_of(id, mm, nn)) return id;
+      grabbed = atomicAdd(p.tile_ctr + my_xcd, 1ull);
+    }
+  };
+  int c_id = blockIdx.x;
+  if (dyn) {
+    issue_grab();
+    if (tid == 0) sh_next = decode_grab();
+    __syncthreads();
+    c_id = sh_next;
+    if (c_id >= total_ids) return;
+  } else {
+    int m0, n0;
+    if (c_id >= total_ids) return;
+    if (!tile_of(c_id, m0, n0)) c_id = next_valid(c_id);
+    if (c_id >= total_ids) return;
+  }
+  load_tile(c_id);
+  issue(0, 0);
+  int buf = 0;
+  bool have_prev = false;
+  int pm0 = 0, pn0 = 0;
+  f32x16 acc[1][NNI];
+  // this lane's fragment addresses inside a stage: row 32 w + li, slots kh and 2 + kh; column li of block 0, k half kh of plane 0
+  const int fa = (wave * 32 + li) * BF3_BK + ((kh ^ ((li >> 2) & 3)) * 4);
+  const int fb = (kh * BN + li) * 4;
+
+  while (c_id < total_ids) {
+    int m0, n0;
+    tile_of(c_id, m0, n0);
+    int n_id = dyn ? total_ids : next_valid(c_id);
+
+    auto stage = [&](int c, auto first_tag) {
+      constexpr bool FIRST = decltype(first_tag)::value;
+      // Stage c was issued a whole stage ago and has had that stage's MFMAs to land.  Nothing but this wave's own vmcnt followed by the
+      // barrier orders LDS-DMA data for the other waves' ds_reads, and the compiler places no wait of its own in this loop.
+      __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+      __syncthreads();  // stage c is complete in `buf`; every wave is done reading buf^1
+      if (dyn) {   // the next tile's number: requested, published one barrier later, read after the next
+        if (FIRST) issue_grab();
+        if (c == 1 && tid == 0) sh_next = decode_grab();
+        if (c == 2) n_id = sh_next;
+      }
+      if (c + 1 < NST) {
+        issue(c + 1, buf ^ 1);
+      } else if (n_id < total_ids) {
+        load_tile(n_id);
+        issue(0, buf ^ 1);
+      }
+      if (FIRST) {
+        // the previous tile's epilogue after this tile's first barrier, then the shift into the released accumulators (see gemm_f32_dma_kernel)
+        if (have_prev) gemm_epilogue_zrows<NNI>(p, acc, pm0, pn0, wave, li, kh);
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int ni = 0; ni < NNI; ++ni) {
+          const float sh = shl[n0 + ni * 32 + li];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[0][ni][r] = sh;
+        }
+      }
+      const float* const ar = As + buf * A_F + fa;
+      const float* const br = Bs + buf * B_F + fb;
+      bf16x8 ah, am, al;
+      bf3_split(*reinterpret_cast<const f32x4*>(ar), *reinterpret_cast<const f32x4*>(As + buf * A_F + (fa ^ 8)), ah, am, al);   // slot 2 + kh: physical slot ^ 2
+      // the six (nine) terms of the k-step, each over the five accumulators: consecutive MFMAs never wait for one another's result
+      bf16x8 bp[3][NNI];
+#pragma unroll
+      for (int ni = 0; ni < NNI; ++ni)
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) bp[pl][ni] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(br + ni * 128 + pl * (2 * BN * 4)));
+      const bf16x8 ap[3] = {ah, am, al};
+      // (a part, b part) in ascending magnitude: 2^-8 (i + j) of the product
+      constexpr int TERMS[9][2] = {{2, 2}, {1, 2}, {2, 1}, {0, 2}, {1, 1}, {2, 0}, {0, 1}, {1, 0}, {0, 0}};
+#pragma unroll
+      for (int k = 0; k < BF3_TERMS; ++k) {
+        const int t = BF3_SMALL_FIRST ? k + (9 - BF3_TERMS) : 8 - k;
+#pragma unroll
+        for (int ni = 0; ni < NNI; ++ni)
+          acc[0][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[TERMS[t][0]], bp[TERMS[t][1]][ni], acc[0][ni], 0, 0, 0);
+      }
+      buf ^= 1;
+    };
+    stage(0, std::true_type{});
+#pragma unroll 1
+    for (int c = 1; c < NST; ++c) stage(c, std::false_type{});
+
+    have_prev = true;
+    pm0 = m0;
+    pn0 = n0;
+    c_id = n_id;
+  }
+  if (have_prev) gemm_epilogue_zrows<NNI>(p, acc, pm0, pn0, wave, li, kh);
+}
+
 // The unrolled DMA loop is instantiated for the K-segment widths of the shipped topologies (256 channels;
 // LSTM inputs of 200 = 2H and 100 = H); anything else takes the register-staged kernel.
 template <bool ZOUT, bool RES>
@@ -1117,6 +1355,18 @@ static bool launch_dma(const GemmParams& p, dim3 grid, dim3 block, hipStream_t s
       }
     }
     return false;
+  }
+  if constexpr (ZOUT) {
+    if (p.nseg == 1 && p.w_bf3 != nullptr && p.N % BF3_BN == 0 && !p.z_f16) {   // the engine's default for these two shapes
+      if (cin == 256) {
+        hipLaunchKernelGGL((gemm_proj_bf16x3_kernel<16, false>), grid, block, 0, stream, p);
+        return true;
+      }
+      if (cin == 200) {
+        hipLaunchKernelGGL((gemm_proj_bf16x3_kernel<13, true>), grid, block, 0, stream, p);
+        return true;
+      }
+    }
   }
   if constexpr (ZOUT) {
     if (p.nseg == 1) {

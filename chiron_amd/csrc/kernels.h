@@ -45,6 +45,10 @@ constexpr int GEMM_MAX_SEG = 16;
 constexpr int GEMM_BM = 128;
 constexpr int GEMM_BN = 128;
 constexpr int GEMM_BK = 32;
+// bf16 x 3 form of the fp32 LSTM projections (gemm_proj_bf16x3_kernel; weight image: weight_pack.h bf16x3_planes)
+constexpr int BF3_BN = 160;                               // columns per tile
+constexpr int BF3_BK = 16;                                // k per stage
+constexpr int BF3_STAGE_BYTES = 3 * 2 * BF3_BN * 8 * 2;   // one stage of one tile: [3 planes][2 k halves][160 columns][8 bf16] = 15360
 
 struct GemmSeg {
   const float* src;  // activation tensor [rows][lda]; nullptr => lift from the signal
@@ -76,6 +80,10 @@ struct GemmParams {
   // weights lost 3 .. 8 x at the logits to that, profiles/r06_split_*) -- and descale[n] = 2^-s[n] is multiplied into the finished
   // accumulator (exact) before the epilogue.
   const float* descale;
+  // fp32 projections (out_mode 1, one K-segment of 256 or 200 channels, N a multiple of 160) as six-term bf16 products: the
+  // weights again as three bf16 planes in the stage images of gemm_proj_bf16x3_kernel (weight_pack.h bf16x3_planes); nullptr:
+  // the fp32 MFMA kernel reads Wt
+  const void* w_bf3;
   int relu;
   // lift (segments with src == nullptr): A = relu(sig[b][in_t]*lift_a[c] + lift_b[c]), 0 outside
   const float* sig;    // [B][L]

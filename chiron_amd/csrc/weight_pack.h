@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -22,6 +24,7 @@ struct ConvGemmPlan {
   float* Wt = nullptr;
   float* shift = nullptr;
   float* descale = nullptr;   // dtype fp32-split: 2^-s[n] of the power-of-two row scaling (GemmParams::descale)
+  void* w_bf3 = nullptr;      // fp32 LSTM projections: Wt as three bf16 planes (bf16x3_planes below; engine.hip builds them after pack_weights)
   int N = 0, Npad = 0, K = 0;
 };
 
@@ -105,6 +108,55 @@ struct HalfPair {
 inline HalfPair split_half(float v) {
   const _Float16 hi = (_Float16)v;
   return {hi, (_Float16)(v - (float)hi)};
+}
+
+// An exact float as three bf16 values: w = hi + mid + lo, each part the next 8 significand bits, cut off (never rounded: FLT_MAX stays
+// finite).  Every part is the fp32 number whose upper 16 bits are stored; the subtractions are exact.  The sum is w itself unless lo
+// falls below fp32's subnormal spacing of bf16 (2^-133), which loses at most that much.
+struct Bf16x3 {
+  uint16_t hi, mid, lo;
+};
+inline uint32_t f32_bits(float v) {
+  uint32_t u;
+  memcpy(&u, &v, 4);
+  return u;
+}
+inline float bits_f32(uint32_t u) {
+  float v;
+  memcpy(&v, &u, 4);
+  return v;
+}
+inline Bf16x3 split_bf16x3(float w) {
+  const uint32_t hb = f32_bits(w) & 0xffff0000u;
+  const float r = w - bits_f32(hb);
+  const uint32_t mb = f32_bits(r) & 0xffff0000u;
+  const float l = r - bits_f32(mb);
+  return {(uint16_t)(hb >> 16), (uint16_t)(mb >> 16), (uint16_t)(f32_bits(l) >> 16)};
+}
+
+// The projection weights of gemm_proj_bf16x3_kernel (gemm.hip): per 160-column tile and 16-k stage one 15 KB image that the LDS-DMA
+// copies as it lies, [plane hi / mid / lo][k half kh][160 columns][8 bf16].  The eight values of (stage c, kh) are
+// k = 16 c + 8 (e >> 2) + 4 kh + (e & 3), e = 0 .. 7: the two 16-byte slots of the fp32 activation row that a lane of half kh splits
+// into the A operand of one v_mfma_f32_32x32x16_bf16.
+inline int bf16x3_stages(int cin) { return (cin + BF3_BK - 1) / BF3_BK; }
+// index (in bf16 elements) of plane `plane` of weight (column n, channel k) in an array of `stages` stages per tile
+inline size_t bf16x3_index(int plane, int n, int k, int stages) {
+  const int tile = n / BF3_BN, col = n % BF3_BN, c = k / BF3_BK, kk = k % BF3_BK;
+  const int kh = (kk >> 2) & 1, e = ((kk >> 3) << 2) | (kk & 3);
+  return ((size_t)(tile * stages + c) * (BF3_STAGE_BYTES / 2)) + (size_t)(((plane * 2 + kh) * BF3_BN + col) * 8 + e);
+}
+// Wt [N][ld] fp32 (k contiguous, the packed fp32 projection weight), N a multiple of 160; channels >= cin are zero in every plane
+inline std::vector<uint16_t> bf16x3_planes(const float* Wt, int N, int ld, int cin) {
+  const int stages = bf16x3_stages(cin);
+  std::vector<uint16_t> v((size_t)(N / BF3_BN) * stages * (BF3_STAGE_BYTES / 2), (uint16_t)0);
+  for (int n = 0; n < N; ++n)
+    for (int k = 0; k < cin; ++k) {
+      const Bf16x3 s = split_bf16x3(Wt[(size_t)n * ld + k]);
+      v[bf16x3_index(0, n, k, stages)] = s.hi;
+      v[bf16x3_index(1, n, k, stages)] = s.mid;
+      v[bf16x3_index(2, n, k, stages)] = s.lo;
+    }
+  return v;
 }
 
 // folded BN (cnn.py:125-163 population branch; association order of the .meta graph):
