@@ -256,6 +256,27 @@ def pileup(args):
     return report
 
 
+def polish(args):
+    """Rescore the pileup's candidate variants with the reads' CTC likelihoods: polish.polish_command (the frames of every read
+    that covers a variant scored against both alleles on the GPU).  Writes <out>/polished.fasta (a valid -g for `map`, `assess` and
+    `pileup`), <out>/polish_variants.tsv and <out>/polish_report.json; exits non-zero on an input without a mapped.sam or when no
+    read could be used."""
+    import logging
+    from . import polish as polish_mod
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    try:
+        report = polish_mod.polish_command(args)
+    except ValueError as e:
+        sys.exit("polish: %s" % e)
+    print("polish: %d candidates, %d scored by %d of %d reads (%d read windows); %d eligible, %d accepted (%d substitutions, %d deletions, "
+          "%d insertions)" % (report["candidates"]["total"], report["candidates"]["scored"], report["reads"]["used"], report["reads"]["total"],
+                              report["items"]["scored"], report["eligible"], report["accepted"]["total"], report["accepted"]["SUB"],
+                              report["accepted"]["DEL"], report["accepted"]["INS"]))
+    if report["reads"]["used"] == 0:
+        sys.exit("polish: no read of %s could be used (%s)" % (report["sam"], report["reads"]["dropped"]))
+    return report
+
+
 def label(args):
     """Labels from the model's own logits: label.label (CTC forced alignment of every read's frames to its reference bases on the
     GPU).  Writes <out>/<read>.signal + <out>/<read>.label, a folder `validate`, `finetune` and `train` take as -i, and
@@ -469,6 +490,32 @@ def build_parser():
     pu.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one genome tile, MiB.")
     pu.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     pu.set_defaults(func=pileup)
+    po = subparsers.add_parser("polish", description="Rescore the pileup's candidate variants with the reads' CTC likelihoods: the frames "
+                               "of every read that covers a variant scored against both alleles on the GPU",
+                               help="Polish a genome with the reads' frame scores: polished sequence, scored variants, report.")
+    po.add_argument("-i", "--input", required=True, help="Output folder of `map --cigar` (its mapped.sam is read), or a SAM file.")
+    po.add_argument("-s", "--signal", required=True, help="Output folder of `call` (its raw/ is read), or a folder of .signal files.")
+    po.add_argument("-g", "--genome", required=True, help="The genome FASTA the reads were mapped to.")
+    po.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder path")
+    po.add_argument("-o", "--output", required=True, help="Folder polished.fasta, polish_variants.tsv and polish_report.json are written to.")
+    po.add_argument("--flank", type=int, default=8, help="Reference bases on either side of a variant in the scored window.")
+    po.add_argument("--min-alt", dest="min_alt", type=int, default=2, help="Fewest reads that must show a variant for it to be a candidate.")
+    po.add_argument("--min-frac", dest="min_frac", type=float, default=0.2, help="Smallest share of the depth that must show it.")
+    po.add_argument("--min-llr", dest="min_llr", type=float, default=0.0,
+                    help="A variant is eligible when its summed log-likelihood ratio exceeds this (not tuned on real reads).")
+    po.add_argument("--min-reads", dest="min_reads", type=int, default=3, help="Fewest reads that must have scored a variant.")
+    po.add_argument("--min-depth", dest="min_depth", type=int, default=3, help="As for `pileup`: the vote's own depth floor (reported only).")
+    po.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
+    po.add_argument("-b", "--batch_size", type=int, default=1100, help="Windows per engine batch.")
+    po.add_argument("--band", type=int, default=256, help="First half-width of the frame alignment's band, in CTC states; 0: the full table.")
+    po.add_argument("--max-band", dest="max_band", type=int, default=8192,
+                    help="Largest half-width the doubling may reach before a read is given up (0: unbounded).")
+    po.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one batch of any stage, MiB.")
+    po.add_argument("--dtype", default="fp32", choices=["fp32", "fp16", "fp16-w2", "fp32-split"], help="Engine arithmetic.")
+    po.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    po.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
+                    help="Use seeded synthetic weights when the model folder has no checkpoint data.")
+    po.set_defaults(func=polish)
     return parser
 
 

@@ -753,6 +753,51 @@ chiron_status chiron_ctc_align(int32_t device_id, const float* scores, const int
                                int32_t* start_out, double* score_out, int32_t* band_out, int32_t* status_out, void* workspace,
                                void* stream);
 
+/* CTC log-likelihoods of many short (frame segment, candidate label) problems that point into one array of frames: what `polish`
+ * asks when it rescores a pileup variant with the reads' frame posteriors.  `scores` is float32 [frames, 5], class 4 = blank, raw
+ * logits, all reads concatenated.  Item i is the frame range [item_begin[i], item_end[i]) of `scores`; items may overlap and may
+ * share frames.  Item i owns the candidates cand_off[i] .. cand_off[i+1]) (cand_off[0] = 0, cand_off[items] = candidates; an item
+ * may own none), and candidate c is labels[label_off[c] .. label_off[c+1]), codes 0..3.  For a candidate of L bases on an item of T
+ * frames x_0 .. x_{T-1}:
+ *
+ * Frame.  Every operand is widened to double first.  m = max_k x_k;  lp_k = (x_k - m) - log(sum_k exp(x_k - m)), the sum taken in
+ * class order 0..4.
+ * States.  s = 0..S-1, S = 2L+1; odd s = 2j+1 is base j (class labels[j]), even s is blank (class 4).
+ * lse(v_1 .. v_n) = m + log(sum_i exp(v_i - m)) with m = max_i v_i, the sum in the order given; -inf when every v_i is -inf.
+ * Recurrence.  alpha_0(0) = lp_0(4), alpha_0(1) = lp_0(labels[0]) when L >= 1, every other alpha_0 is -inf;
+ *     alpha_t(s) = lse(alpha_{t-1}(s), alpha_{t-1}(s-1), alpha_{t-1}(s-2)) + lp_t(class(s)).
+ * A predecessor below state 0 is -inf, and so is the s-2 predecessor unless s is odd and base j differs from base j-1: the repeat
+ * rule of chiron_ctc_align.
+ * Result.  loglik = lse(alpha_{T-1}(S-1), alpha_{T-1}(S-2)) (the second operand only when S >= 2): natural log, double, never
+ * rounded to float.  A restatement in numpy float64 differs by the rounding of exp and log alone, a few ulp per frame.
+ *
+ * status_out: 0 scored; 1 infeasible, T < L + the number of adjacent equal bases (T = 0 with L > 0 included): loglik is -inf.
+ * L = 0 is legal: the sum of the blank log-probabilities, 0.0 when T = 0 as well.
+ *
+ * Host arrays in, host arrays out: scores, item_begin, item_end [items], cand_off [items + 1], labels, label_off [candidates + 1],
+ * loglik_out and status_out [candidates] are HOST memory; workspace is device memory on device_id of the size function's bytes for
+ * the same frames, items, candidates and label_bytes = label_off[candidates] - label_off[0] (larger values are fine).  It holds the
+ * copied scores, the double log-softmax of EVERY frame of the call ([frames][5], computed once by score_softmax_kernel, whether an
+ * item covers the frame or not), a 24-byte record per candidate, the labels and the results; `items` is checked and costs nothing.
+ * Runs on `stream` (a hipStream_t; NULL = the null stream) and synchronises it before returning.  flags: 0 (reserved).
+ * CHIRON_ERR_INVALID: a negative size, a negative or decreasing offset, cand_off that does not run from 0 to candidates, an item
+ * outside [0, frames], a code above 3, a score that is not finite (any frame of the call).  CHIRON_ERR_OVERFLOW: an item above
+ * CHIRON_SCORE_MAX_FRAMES, a candidate above CHIRON_SCORE_MAX_LABEL bases, more than 2^24 candidates or items, more than 2^40
+ * frames, label_bytes above candidates * CHIRON_SCORE_MAX_LABEL.  All of it before anything is copied or launched.  items == 0 or
+ * candidates == 0 is a no-op (size 0).
+ * ctc_score_kernel: one wavefront per candidate, CHIRON_SCORE_THREADS / 64 to a workgroup, candidate c on wave c mod the launch's
+ * waves, at most CHIRON_SCORE_MAX_GROUPS workgroups; no atomics, so a candidate's value is bitwise the same whatever else the call
+ * holds and in whatever order; every offset the kernels form is 64-bit.  The size function is host-only.                        */
+#define CHIRON_SCORE_MAX_FRAMES 4096   /* frames of one item                                                                      */
+#define CHIRON_SCORE_MAX_LABEL 127     /* bases of one candidate: S <= 255 states, four to a lane                                 */
+#define CHIRON_SCORE_THREADS 256
+#define CHIRON_SCORE_MAX_GROUPS 2048   /* workgroups of one launch                                                                */
+chiron_status chiron_ctc_score_workspace_size(int64_t frames, int64_t items, int64_t candidates, int64_t label_bytes, size_t* bytes);
+chiron_status chiron_ctc_score(int32_t device_id, const float* scores, int64_t frames, const int64_t* item_begin,
+                               const int64_t* item_end, const int64_t* cand_off, int64_t items, const uint8_t* labels,
+                               const int64_t* label_off, int64_t candidates, uint32_t flags, double* loglik_out, int32_t* status_out,
+                               void* workspace, void* stream);
+
 /* Pileup: per genome position, what the mapped reads say there, and the consensus call.  An alignment is (pos, read, ops): pos a
  * position in concatenated genome coordinates, read the read in genome orientation (codes 0..4), ops one byte per column as
  * chiron_align_trace codes them (0 '=', 1 'X', 2 'I', 3 'D'); its '=', 'X' and 'I' columns together consume exactly the read, and m
