@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/chiron_amd.h"
+#include "bitvector.h"
 #include "host_entry.h"
 #include "kernels.h"
 
@@ -248,25 +249,6 @@ __global__ __launch_bounds__(64) void ctc_beta_kernel(const CtcParams p) {
       g[(size_t)t * CTC_K + lane] = y - c * inv;
     }
   }
-}
-
-// Myers' block step: one column of the DP for one 64-row block.  hin/hout: horizontal delta entering / leaving the block.
-__device__ __forceinline__ int advance_block(uint64_t& Pv, uint64_t& Mv, uint64_t Eq, int hin, uint64_t high) {
-  const uint64_t Xv = Eq | Mv;
-  if (hin < 0) Eq |= 1ull;
-  const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-  uint64_t Ph = Mv | ~(Xh | Pv);
-  uint64_t Mh = Pv & Xh;
-  int hout = 0;
-  if (Ph & high) hout += 1;
-  if (Mh & high) hout -= 1;
-  Ph <<= 1;
-  Mh <<= 1;
-  if (hin < 0) Mh |= 1ull;
-  else if (hin > 0) Ph |= 1ull;
-  Pv = Mh | ~(Xv | Ph);
-  Mv = Ph & Xv;
-  return hout;
 }
 
 __device__ int64_t lower_bound_row(const int64_t* indices, int64_t nnz, int64_t row) {

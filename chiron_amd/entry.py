@@ -305,6 +305,24 @@ def label(args):
     return report
 
 
+def demux(args):
+    """Split called reads by barcode and trim their ends: demux.demux_command (every read end searched for every barcode on the GPU).
+    Writes <out>/<barcode>.fastq per bin (each a valid -i of `map` and `assess`), <out>/unclassified.fastq, <out>/demux.tsv and
+    <out>/demux_report.json; exits non-zero on an input without reads or a barcode file without usable records."""
+    from . import demux as demux_mod
+    try:
+        report = demux_mod.demux_command(args.input, args.barcodes, args.output, window=args.window, max_err=args.max_err,
+                                         min_margin=args.min_margin, require=args.require, do_trim=not args.no_trim,
+                                         workspace_mb=args.workspace_mb, device_id=args.device)
+    except ValueError as e:
+        sys.exit("demux: %s" % e)
+    s = report["status"]
+    print("demux: %d reads against %d patterns; %d classified into %d bins, %d unclassified, %d in conflict, %d empty after trimming; "
+          "%d of %d bases written" % (report["reads"], report["patterns"], s["classified"], sum(1 for v in report["bins"].values() if v),
+                                      s["unclassified"], s["conflict"], s["empty"], report["bases"]["written"], report["bases"]["in"]))
+    return report
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -516,6 +534,29 @@ def build_parser():
     po.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
                     help="Use seeded synthetic weights when the model folder has no checkpoint data.")
     po.set_defaults(func=polish)
+    dm = subparsers.add_parser("demux", description="Split the called reads of a multiplexed run by barcode and cut barcode and adapter "
+                               "sequence off their ends: the first and last bases of every read searched for every barcode on the GPU, "
+                               "exactly, by edit distance",
+                               help="Split called reads by barcode and trim their ends.")
+    dm.add_argument("-i", "--input", required=True, help="Output folder of `call` (its result/ is read), or a fasta/fastq file or folder.")
+    dm.add_argument("--barcodes", required=True,
+                    help="FASTA of the barcodes as they read at a read's start, 1 to 64 bases each; records that share a name are spellings "
+                         "of one barcode.  A file with a single adapter is plain adapter trimming into one bin.")
+    dm.add_argument("-o", "--output", required=True,
+                    help="Folder <barcode>.fastq per bin (.fasta when the input has no qualities), unclassified.<ext>, demux.tsv and "
+                         "demux_report.json are written to.")
+    dm.add_argument("--window", type=int, default=150, help="Bases of either read end that are searched (not tuned on real reads).")
+    dm.add_argument("--max-err", dest="max_err", type=float, default=0.2,
+                    help="An end hits when its best barcode lies within this share of the barcode's length in edits (not tuned on real reads).")
+    dm.add_argument("--min-margin", dest="min_margin", type=int, default=2,
+                    help="... and the best other barcode is at least this many edits worse (not tuned on real reads).")
+    dm.add_argument("--require", default="either", choices=["either", "both"],
+                    help="either: one end's hit names the barcode; both: the two ends must hit and agree.  Two hits that disagree are a "
+                         "conflict in either mode.")
+    dm.add_argument("--no-trim", dest="no_trim", action="store_true", help="Write the classified reads whole.")
+    dm.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one search call, MiB.")
+    dm.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    dm.set_defaults(func=demux)
     return parser
 
 

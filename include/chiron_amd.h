@@ -798,6 +798,61 @@ chiron_status chiron_ctc_score(int32_t device_id, const float* scores, int64_t f
                                const int64_t* label_off, int64_t candidates, uint32_t flags, double* loglik_out, int32_t* status_out,
                                void* workspace, void* stream);
 
+/* Demultiplexing: which of a fixed set of short patterns (barcodes, adapters) lies in each of very many short windows (read ends),
+ * how well, and where it ends.  Codes as everywhere else: 0..3, and 4 matches nothing, on either side.  A pattern p has n bases,
+ * 1 <= n <= CHIRON_DEMUX_MAX_PATTERN; a window t has m bases, 0 <= m <= CHIRON_DEMUX_MAX_WINDOW.
+ *
+ * Per pair.  For e = 0..m let D(e) be the smallest unit-cost edit distance of p against any substring of t that ends at e (t[s:e),
+ * 0 <= s <= e; the empty substring included, so D(e) <= n and D(0) = n).  The pair's result is (E, e): the smallest D, then the
+ * smallest e that attains it.  It is a property of the inputs.  E equals the E of chiron_align_infix for the same pair; e need not
+ * equal that call's e, which orders by matching columns before it orders by position.  Only the end is reported: a caller that needs
+ * the inner boundary of a pattern at a read's tail hands the window in reversed.
+ * Per window, over the call's patterns q = 0 .. patterns-1 with their group numbers pat_group[q] >= 0:
+ *   best    the pattern with the smallest E, ties to the smaller q
+ *   dist    that pattern's E
+ *   end     that pattern's e
+ *   second  the smallest E over the patterns whose pat_group differs from pat_group[best]; CHIRON_DEMUX_NONE when there is none
+ * Groups let one barcode have several spellings that do not compete with each other.
+ * Optional matrix.  When pair_dist_out and pair_end_out are both non-NULL, every pair's E and e are written as well, int16
+ * [windows][patterns]; both NULL: not computed apart from what the window results need, not copied.  One NULL and one not is refused.
+ *
+ * demux_kernel (csrc/demux.hip): the bit-parallel edit-distance automaton of Myers in Hyyro's form, one pattern a lane, a pattern
+ * column one 64-bit word, the first row free (horizontal input 0), exact at any distance.  With P2 the smallest power of two >=
+ * min(patterns, 64), a wavefront serves 64 / P2 windows at once: lane l belongs to window slot l / P2 and takes the patterns
+ * l % P2, l % P2 + P2, ... (more than one only when P2 = 64).  CHIRON_DEMUX_THREADS / 64 waves a workgroup, at most
+ * CHIRON_DEMUX_MAX_GROUPS workgroups, slot groups dealt to the launch's waves round-robin.  No LDS, no atomics, every offset 64-bit;
+ * a window's outputs depend on that window and the patterns alone, whatever else the call holds and in whatever order.
+ *
+ * Workspace (device memory), each part rounded up to 256 bytes: 40 bytes a pattern (four match masks, length, group), 16 bytes of
+ * record and 16 of results a window, window_bytes + 8 windows bytes of codes (every window starts on an 8-byte boundary) and, with
+ * want_matrix != 0, two int16 [windows][patterns].  Larger values of any argument are fine.  Host-only.  CHIRON_ERR_INVALID: a
+ * negative argument, patterns == 0.  CHIRON_ERR_OVERFLOW: windows > 2^24, patterns > CHIRON_DEMUX_MAX_PATTERNS, window_bytes >
+ * windows * CHIRON_DEMUX_MAX_WINDOW.  windows == 0 gives 0.                                                                        */
+#define CHIRON_DEMUX_MAX_PATTERN 64     /* bases of one pattern: one 64-bit word a column                                          */
+#define CHIRON_DEMUX_MAX_WINDOW 4096    /* bases of one window                                                                     */
+#define CHIRON_DEMUX_MAX_PATTERNS 65536 /* patterns of one call: (E, q) is one 32-bit key                                          */
+#define CHIRON_DEMUX_THREADS 256
+#define CHIRON_DEMUX_MAX_GROUPS 2048    /* workgroups of one launch                                                                */
+#define CHIRON_DEMUX_NONE 0x7FFFFFFF    /* second_out of a window whose patterns all share one group                               */
+chiron_status chiron_demux_workspace_size(int64_t windows, int64_t window_bytes, int64_t patterns, int32_t want_matrix, size_t* bytes);
+
+/* Classify `windows` windows against `patterns` patterns in one launch.  win_codes, pat_codes: HOST bytes; window w is
+ * win_codes[win_off[w] .. win_off[w+1]) and pattern q is pat_codes[pat_off[q] .. pat_off[q+1]); win_off is HOST int64 [windows + 1],
+ * pat_off HOST int64 [patterns + 1], both non-negative and non-decreasing; pat_group is HOST int32 [patterns].  best_out, dist_out,
+ * end_out, second_out: HOST int32 [windows].  pair_dist_out, pair_end_out: HOST int16 [windows][patterns], or both NULL.  workspace:
+ * device memory on device_id of chiron_demux_workspace_size(windows, win_off[windows] - win_off[0], patterns, matrix wanted) bytes.
+ * flags: 0 (reserved).  The host packs every pattern's length and four match masks (bit i of mask c set when base i is c; a code 4
+ * sets no bit), copies them and the windows in, runs on `stream` (a hipStream_t; NULL = the null stream) and synchronises it
+ * before returning.  CHIRON_ERR_INVALID: unknown flags, a negative count, patterns == 0, a null array, one matrix array without the
+ * other, a negative or decreasing offset, a code above 4, a pattern of 0 bases, a negative group.  CHIRON_ERR_OVERFLOW: a pattern
+ * above CHIRON_DEMUX_MAX_PATTERN bases, a window above CHIRON_DEMUX_MAX_WINDOW, more than 2^24 windows, more than
+ * CHIRON_DEMUX_MAX_PATTERNS patterns.  All of it before anything is copied or launched.  windows == 0 is a no-op that touches no
+ * device (the counts are still checked).                                                                                           */
+chiron_status chiron_demux_windows(int32_t device_id, const uint8_t* win_codes, const int64_t* win_off, int64_t windows,
+                                   const uint8_t* pat_codes, const int64_t* pat_off, const int32_t* pat_group, int64_t patterns,
+                                   uint32_t flags, int32_t* best_out, int32_t* dist_out, int32_t* end_out, int32_t* second_out,
+                                   int16_t* pair_dist_out, int16_t* pair_end_out, void* workspace, void* stream);
+
 /* Pileup: per genome position, what the mapped reads say there, and the consensus call.  An alignment is (pos, read, ops): pos a
  * position in concatenated genome coordinates, read the read in genome orientation (codes 0..4), ops one byte per column as
  * chiron_align_trace codes them (0 '=', 1 'X', 2 'I', 3 'D'); its '=', 'X' and 'I' columns together consume exactly the read, and m
