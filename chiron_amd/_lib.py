@@ -267,6 +267,26 @@ def pack_pairs(a, b):
     return codes, lens_a, lens_b, off_a, off_b
 
 
+alloc_hook = None   # tests only: an object whose byte_buffer(nbytes, device) and output(shape, dtype, device) replace torch.empty below
+
+
+def device_bytes(nbytes, device, at_least=0):
+    """The uint8 device buffer (tape, workspace) of one call, uninitialised: max(nbytes, at_least) bytes.  With alloc_hook set,
+    whatever the hook returns for exactly nbytes."""
+    if alloc_hook is not None:
+        return alloc_hook.byte_buffer(int(nbytes), device)
+    import torch
+    return torch.empty(max(int(nbytes), at_least), dtype=torch.uint8, device=device)
+
+
+def device_output(shape, dtype, device):
+    """An output tensor the library fills, uninitialised.  With alloc_hook set, whatever the hook returns for that shape and dtype."""
+    if alloc_hook is not None:
+        return alloc_hook.output(tuple(shape), dtype, device)
+    import torch
+    return torch.empty(tuple(shape), dtype=dtype, device=device)
+
+
 def device_workspace(nbytes, device_id, who, what):
     """The workspace of one call on the GPU.  nbytes: the size, or a function that asks the library for it -- called here, after
     torch is imported (its ROCm runtime has to come up before the library loads, see above) and before the GPU is touched, so
@@ -278,5 +298,5 @@ def device_workspace(nbytes, device_id, who, what):
     if not torch.cuda.is_available():
         raise RuntimeError("chiron_amd.%s needs a GPU: the %s has no CPU fallback" % (who, what))
     dev = torch.device("cuda", device_id)
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    ws = device_bytes(nbytes, dev, at_least=256)
     return lib, ws, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

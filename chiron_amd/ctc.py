@@ -59,9 +59,9 @@ def _launch(logits, seq_len, labels, label_len, want_grad, check=True):
     flags = (_lib.CTC_WANT_GRAD if want_grad else 0) | (0 if check else _lib.CTC_TRUSTED)
     nbytes = C.c_size_t()
     _lib.check(lib.chiron_ctc_workspace_size(B, T, lmax, flags, C.byref(nbytes)))
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    grad = torch.empty((B, T, _lib.CLASSES), dtype=torch.float32, device=dev) if want_grad else None
-    ws = torch.empty(max(int(nbytes.value), 4), dtype=torch.uint8, device=dev) if want_grad else None
+    loss = _lib.device_output((B,), torch.float32, dev)
+    grad = _lib.device_output((B, T, _lib.CLASSES), torch.float32, dev) if want_grad else None
+    ws = _lib.device_bytes(nbytes.value, dev, at_least=4) if want_grad else None
     stream = torch.cuda.current_stream(dev)
     if B > 0:
         _lib.check(lib.chiron_ctc_loss(dev.index if dev.index is not None else torch.cuda.current_device(), logits.data_ptr(),

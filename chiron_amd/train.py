@@ -60,9 +60,9 @@ def rnn_forward(spec, params, features, seq_len):
     B, T, _ = features.shape
     tape_b, ws_b = train_sizes(spec, B, T)
     dev = features.device
-    logits = torch.empty((B, T, _lib.CLASSES), dtype=torch.float32, device=dev)
-    tape = torch.empty(tape_b, dtype=torch.uint8, device=dev)
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    logits = _lib.device_output((B, T, _lib.CLASSES), torch.float32, dev)
+    tape = _lib.device_bytes(tape_b, dev)
+    ws = _lib.device_bytes(ws_b, dev)
     desc = spec.to_c()
     _lib.check(_lib.load().chiron_rnn_train_forward(_device_index(features), C.byref(desc), params.data_ptr(), features.data_ptr(),
                                                     seq_len.data_ptr(), B, T, logits.data_ptr(), tape.data_ptr(), ws.data_ptr(),
@@ -75,8 +75,8 @@ def rnn_backward(spec, params, features, seq_len, dlogits, tape, ws, want_dfeatu
     torch = _torch()
     B, T, _ = features.shape
     dev = features.device
-    dparams = torch.empty_like(params)
-    dfeat = torch.empty_like(features) if want_dfeatures else None
+    dparams = _lib.device_output(params.shape, params.dtype, params.device)
+    dfeat = _lib.device_output(features.shape, features.dtype, dev) if want_dfeatures else None
     desc = spec.to_c()
     _lib.check(_lib.load().chiron_rnn_train_backward(_device_index(features), C.byref(desc), params.data_ptr(), features.data_ptr(),
                                                      seq_len.data_ptr(), dlogits.data_ptr(), B, T, tape.data_ptr(), ws.data_ptr(),
@@ -377,10 +377,10 @@ def cnn_forward(spec, params, signal):
     B, L = signal.shape
     tape_b, ws_b = cnn_train_sizes(spec, B, L)
     dev = signal.device
-    feats = torch.empty((B, spec.output_len(L), spec.blocks[-1]["out"]), dtype=torch.float32, device=dev)
+    feats = _lib.device_output((B, spec.output_len(L), spec.blocks[-1]["out"]), torch.float32, dev)
     moments = torch.zeros_like(params)
-    tape = torch.empty(tape_b, dtype=torch.uint8, device=dev)
-    ws = torch.empty(ws_b, dtype=torch.uint8, device=dev)
+    tape = _lib.device_bytes(tape_b, dev)
+    ws = _lib.device_bytes(ws_b, dev)
     desc = spec.to_c()
     _lib.check(_lib.load().chiron_cnn_train_forward(_device_index(signal), C.byref(desc), params.data_ptr(), signal.data_ptr(), B, L,
                                                     feats.data_ptr(), moments.data_ptr(), tape.data_ptr(), ws.data_ptr(),
@@ -411,7 +411,7 @@ def cnn_backward(spec, params, signal, dfeatures, tape, ws):
     """chiron_cnn_train_backward -> dparams [n] (exactly 0 in the pop_mean / pop_var slots)."""
     torch = _torch()
     B, L = signal.shape
-    dparams = torch.empty_like(params)
+    dparams = _lib.device_output(params.shape, params.dtype, params.device)
     desc = spec.to_c()
     _lib.check(_lib.load().chiron_cnn_train_backward(_device_index(signal), C.byref(desc), params.data_ptr(), signal.data_ptr(),
                                                      dfeatures.data_ptr(), B, L, tape.data_ptr(), ws.data_ptr(), dparams.data_ptr(),

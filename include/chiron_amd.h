@@ -410,7 +410,20 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  * Workspace: with CHIRON_CTC_WANT_GRAD the forward pass keeps alpha of every frame, in double, for the backward pass,
  *   bytes = batch * T * S_max * 8,   S_max = 2 * min(max_label_len, T) + 1,
  * and 0 bytes without it.  Host-only (no GPU needed).  CHIRON_ERR_OVERFLOW when T > CHIRON_CTC_MAX_T or max_label_len >
- * CHIRON_CTC_MAX_LABEL; within those bounds every workspace stays below 2^62 bytes and every offset the kernels form is 64-bit.  */
+ * CHIRON_CTC_MAX_LABEL; within those bounds every workspace stays below 2^62 bytes and every offset the kernels form is 64-bit.
+ *
+ * Caller's memory.  This holds for every call below that takes a workspace, a tape or a device output buffer from its caller --
+ * chiron_ctc_loss, chiron_rnn_train_forward / _backward, chiron_cnn_train_forward / _backward, chiron_align_pairs,
+ * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows and
+ * chiron_pileup; their own comments say "uninitialised" or name the size function and mean this:
+ *   - workspace, tape and output buffers may hold anything on entry: the results do not depend on it (the library clears what it
+ *     needs cleared, on the call's stream);
+ *   - every element of every output is written, the rows and frames that carry no result included (frames past seq_len, skipped and
+ *     infeasible rows, the pop_mean / pop_var slots of a gradient).  The two exceptions are stated where they apply: moments_out of
+ *     chiron_cnn_train_forward (only the statistics' slots are written) and a failed pair's slice of chiron_align_trace's ops_out;
+ *   - nothing outside the bytes that the call's *_workspace_size / *_train_sizes function names, and outside the outputs' own
+ *     extents, is read or written: a caller may pack other data right behind a workspace of exactly that size.
+ * tests/test_gpu_workspace.py holds every one of these calls to the three parts.                                                 */
 #define CHIRON_CTC_WANT_GRAD 1u
 #define CHIRON_CTC_TRUSTED 2u   /* chiron_ctc_loss: the caller has checked seq_len / labels / label_len: no read-back, no sync */
 #define CHIRON_CTC_MAX_T 8192
@@ -420,7 +433,7 @@ chiron_status chiron_ctc_workspace_size(int32_t batch, int32_t T, int32_t max_la
 /* Stand-alone CTC loss (and, with CHIRON_CTC_WANT_GRAD, its gradient) for torch users: every operand is a device pointer on
  * device_id.  logits float32 [batch, T, 5]; seq_len int32 [batch]; labels int32 [batch, max_label_len] dense, padded; label_len
  * int32 [batch]; loss_out float32 [batch]; grad_out float32 [batch, T, 5] (written only with CHIRON_CTC_WANT_GRAD); workspace of
- * chiron_ctc_workspace_size bytes (NULL without the flag).  Asynchronous on `stream` (a hipStream_t; NULL = the null stream), with
+ * chiron_ctc_workspace_size bytes (NULL without the flag; "Caller's memory" above).  Asynchronous on `stream` (a hipStream_t; NULL = the null stream), with
  * one exception: seq_len, labels and label_len are first read back on `stream` (a small synchronous copy) and checked, so that an
  * argument error returns CHIRON_ERR_INVALID before anything is launched: a label outside 0..3, label_len < 0 or > max_label_len,
  * seq_len < 0 or > T, batch < 0.  With CHIRON_CTC_TRUSTED that read-back is skipped and the call is fully asynchronous; the
@@ -466,7 +479,7 @@ chiron_status chiron_rnn_train_sizes(const chiron_model_desc* desc, int32_t batc
  * chiron_engine_features) and seq_len int32 [batch], with the semantics of the inference layers: gate order i, j, f, o; forget bias
  * +1.0; frames t >= seq_len[b] emit 0 and carry the state; the backward direction runs over the first seq_len[b] frames reversed
  * (seq_len is clamped to 0..T).  params: the slice of chiron_rnn_params_range.  Every pointer is device memory on device_id; tape
- * and workspace of chiron_rnn_train_sizes bytes, uninitialised.  Asynchronous on `stream` (a hipStream_t; NULL = the null stream);
+ * and workspace of chiron_rnn_train_sizes bytes, uninitialised ("Caller's memory" above).  Asynchronous on `stream` (a hipStream_t; NULL = the null stream);
  * argument errors are reported before anything is launched.                                                                       */
 chiron_status chiron_rnn_train_forward(int32_t device_id, const chiron_model_desc* desc, const float* params, const float* features,
                                        const int32_t* seq_len, int32_t batch, int32_t T, float* logits_out, void* tape, void* workspace,
@@ -521,7 +534,7 @@ chiron_status chiron_cnn_train_tape_relu(const chiron_model_desc* desc, int32_t 
  * params: the section of chiron_cnn_params_range; its pop_mean / pop_var slots are not read.  moments_out has the layout of
  * params; only the pop_mean / pop_var slots are written: each site's batch mean and biased variance (the moving averages are the
  * caller's arithmetic, cnn.py:153-156).  Every pointer is device memory on device_id, 16-byte aligned; tape and workspace of
- * chiron_cnn_train_sizes bytes, uninitialised.  Asynchronous on `stream` (a hipStream_t; NULL = the null stream); argument errors
+ * chiron_cnn_train_sizes bytes, uninitialised ("Caller's memory" above).  Asynchronous on `stream` (a hipStream_t; NULL = the null stream); argument errors
  * are reported before anything is launched.                                                                                      */
 chiron_status chiron_cnn_train_forward(int32_t device_id, const chiron_model_desc* desc, const float* params, const float* signal,
                                        int32_t batch, int32_t segment_len, float* features_out, float* moments_out, void* tape,
@@ -565,7 +578,7 @@ chiron_status chiron_align_workspace_size(int64_t pairs, int64_t max_len, size_t
 /* Align `pairs` pairs in one launch.  codes: HOST bytes; pair p's read is codes[read_off[p] .. read_off[p+1]) and its reference
  * codes[ref_off[p] .. ref_off[p+1]); read_off and ref_off are HOST int64 [pairs + 1], non-negative and non-decreasing (the two
  * may interleave in any way; typically all reads, then all references).  edit_out, match_out, band_out: HOST int32 [pairs].
- * workspace: device memory on device_id of chiron_align_workspace_size(pairs, longest sequence) bytes.  flags: 0 (reserved).
+ * workspace: device memory on device_id of chiron_align_workspace_size(pairs, longest sequence) bytes ("Caller's memory" above).  flags: 0 (reserved).
  * Runs on `stream` (a hipStream_t; NULL = the null stream) and synchronises it before returning.  CHIRON_ERR_INVALID for a bad
  * offset or a code above 4, CHIRON_ERR_OVERFLOW for a sequence longer than CHIRON_ALIGN_MAX_LEN, both before anything is copied
  * or launched.  pairs == 0 is a no-op.                                                                                         */
@@ -602,7 +615,7 @@ chiron_status chiron_align_trace_workspace_size(int64_t pairs, int64_t backpoint
  * p's columns are ops_out[ops_off[p] .. ops_off[p+1]), first column first, and ops_off[p+1] - ops_off[p] must be the pair's
  * column count n + m - M - X = E + M.  status_out: HOST int32 [pairs]: 0 traced; 1 the kernel's own (E, M) of the pair is not
  * the one passed in, and the pair's slice of ops_out is left untouched (the other pairs are unaffected).  workspace: device memory
- * on device_id of chiron_align_trace_workspace_size bytes for the call's pairs.  flags: 0 (reserved).  Runs on `stream` (a
+ * on device_id of chiron_align_trace_workspace_size bytes for the call's pairs ("Caller's memory" above).  flags: 0 (reserved).  Runs on `stream` (a
  * hipStream_t; NULL = the null stream) and synchronises it before returning.  CHIRON_ERR_INVALID for a bad offset, a code above
  * 4, edit < |m-n|, edit > max(n, m), a match count the lengths and edit rule out, or an ops_off that disagrees with the column
  * count; CHIRON_ERR_OVERFLOW for a sequence longer than CHIRON_ALIGN_MAX_LEN; all before anything is copied or launched.
@@ -643,7 +656,7 @@ chiron_status chiron_align_infix_workspace_size(int64_t pairs, int64_t max_read,
 /* Align `pairs` pairs in one launch.  codes: HOST bytes; pair p's read is codes[read_off[p] .. read_off[p+1]) and its window
  * codes[win_off[p] .. win_off[p+1]); read_off and win_off are HOST int64 [pairs + 1], non-negative and non-decreasing.  edit_out,
  * match_out, start_out, end_out, band_out: HOST int32 [pairs]; start and end are offsets into the pair's window.  workspace:
- * device memory on device_id of chiron_align_infix_workspace_size(pairs, longest read, longest window) bytes.  flags: 0
+ * device memory on device_id of chiron_align_infix_workspace_size(pairs, longest read, longest window) bytes ("Caller's memory" above).  flags: 0
  * (reserved).  Runs on `stream` (a hipStream_t; NULL = the null stream) and synchronises it before returning.
  * CHIRON_ERR_INVALID for a bad offset, a code above 4 or band0 < 0, CHIRON_ERR_OVERFLOW for a read or window past its limit, all
  * before anything is copied or launched.  pairs == 0 is a no-op.                                                                */
@@ -686,7 +699,7 @@ chiron_status chiron_seed_workspace_size(int64_t n_index, int64_t genome_len, in
 /* Seed `reads` reads in one launch.  idx_val (uint32) and idx_pos (int32): HOST [n_index], as above.  codes: HOST bytes; read q is
  * codes[read_off[q] .. read_off[q+1]); read_off is HOST int64 [reads + 1], non-negative and non-decreasing.  votes_out,
  * second_out, strand_out (0 forward, 1 reverse): HOST int32 [reads]; delta_out, g_out: HOST int64 [reads].  workspace: device
- * memory on device_id of chiron_seed_workspace_size(n_index, genome_len, reads, longest read, sum of the reads) bytes.  flags: 0
+ * memory on device_id of chiron_seed_workspace_size(n_index, genome_len, reads, longest read, sum of the reads) bytes ("Caller's memory" above).  flags: 0
  * (reserved).  The call keeps no state: it copies the index and the reads in, runs on `stream` (a hipStream_t; NULL = the null
  * stream) and synchronises it before returning.  CHIRON_ERR_INVALID for a null operand, unknown flags, a negative count, a bad
  * offset, a code above 4, an index that is not sorted or holds a position outside 0 .. genome_len - k; CHIRON_ERR_OVERFLOW past
@@ -733,7 +746,7 @@ chiron_status chiron_seed_reads(int32_t device_id, const uint32_t* idx_val, cons
  *
  * Host arrays in, host arrays out: scores, frame_off, labels, label_off, start_out [label_off[reads]], score_out, band_out,
  * status_out [reads] are HOST memory; workspace is device memory on device_id of the size function's bytes for the same offsets,
- * band0 and max_band.  It holds the copied inputs and results, two recursion rows of doubles per workgroup for bands wider than
+ * band0 and max_band ("Caller's memory" above).  It holds the copied inputs and results, two recursion rows of doubles per workgroup for bands wider than
  * CHIRON_LABEL_LDS_SLOTS states, and the 2-bit back-pointer cells of every read at the widest band that read can reach.  Runs on
  * `stream` (a hipStream_t; NULL = the null stream) and synchronises it before returning.  flags: 0 (reserved).
  * CHIRON_ERR_INVALID: decreasing or negative offsets, a code above 3, a score that is not finite, band0 < 0, max_band < 0,
@@ -776,7 +789,8 @@ chiron_status chiron_ctc_align(int32_t device_id, const float* scores, const int
  *
  * Host arrays in, host arrays out: scores, item_begin, item_end [items], cand_off [items + 1], labels, label_off [candidates + 1],
  * loglik_out and status_out [candidates] are HOST memory; workspace is device memory on device_id of the size function's bytes for
- * the same frames, items, candidates and label_bytes = label_off[candidates] - label_off[0] (larger values are fine).  It holds the
+ * the same frames, items, candidates and label_bytes = label_off[candidates] - label_off[0] (larger values are fine;
+ * "Caller's memory" above).  It holds the
  * copied scores, the double log-softmax of EVERY frame of the call ([frames][5], computed once by score_softmax_kernel, whether an
  * item covers the frame or not), a 24-byte record per candidate, the labels and the results; `items` is checked and costs nothing.
  * Runs on `stream` (a hipStream_t; NULL = the null stream) and synchronises it before returning.  flags: 0 (reserved).
@@ -840,7 +854,7 @@ chiron_status chiron_demux_workspace_size(int64_t windows, int64_t window_bytes,
  * win_codes[win_off[w] .. win_off[w+1]) and pattern q is pat_codes[pat_off[q] .. pat_off[q+1]); win_off is HOST int64 [windows + 1],
  * pat_off HOST int64 [patterns + 1], both non-negative and non-decreasing; pat_group is HOST int32 [patterns].  best_out, dist_out,
  * end_out, second_out: HOST int32 [windows].  pair_dist_out, pair_end_out: HOST int16 [windows][patterns], or both NULL.  workspace:
- * device memory on device_id of chiron_demux_workspace_size(windows, win_off[windows] - win_off[0], patterns, matrix wanted) bytes.
+ * device memory on device_id of chiron_demux_workspace_size(windows, win_off[windows] - win_off[0], patterns, matrix wanted) bytes ("Caller's memory" above).
  * flags: 0 (reserved).  The host packs every pattern's length and four match masks (bit i of mask c set when base i is c; a code 4
  * sets no bit), copies them and the windows in, runs on `stream` (a hipStream_t; NULL = the null stream) and synchronises it
  * before returning.  CHIRON_ERR_INVALID: unknown flags, a negative count, patterns == 0, a null array, one matrix array without the
@@ -898,7 +912,7 @@ chiron_status chiron_pileup_workspace_size(int64_t alignments, int64_t read_byte
  * deleted), byte 1 the number of inserted bases emitted, bytes 2..5 their codes (unused ones 0), byte 6 the status (0 called, 1 low
  * depth), byte 7 zero; clipped_out int64 [1], the clipped 'I' columns of ALL alignments of the call: it does not depend on the tile
  * (a caller that tiles a genome takes it from a call that holds every alignment once, or sums it over disjoint sets).  workspace:
- * device memory on device_id of chiron_pileup_workspace_size(alignments, read bytes, column bytes, g1 - g0) bytes.  flags: 0
+ * device memory on device_id of chiron_pileup_workspace_size(alignments, read bytes, column bytes, g1 - g0) bytes ("Caller's memory" above).  flags: 0
  * (reserved).  Runs on `stream` (a hipStream_t; NULL = the null stream) -- a clear of the count planes, pileup_count_kernel (one
  * workgroup of CHIRON_PILEUP_THREADS per alignment, alignment p on workgroup p mod the launch's group count, relaxed int32 atomic
  * adds; every offset 64-bit) and pileup_call_kernel (one thread per position) -- and synchronises it before returning.
