@@ -323,6 +323,26 @@ def demux(args):
     return report
 
 
+def squiggle(args):
+    """The reads' current levels on the genome: squiggle.squiggle_command (the samples of every called base reduced to a level and the
+    levels summed per position and strand on the GPU).  Writes <out>/levels.tsv and <out>/squiggle_report.json, with --control
+    <out>/compare.tsv (Welch's t per position against the control sample), with --kmer <out>/kmer_levels.tsv and with --events
+    <out>/events/<read>.tsv; exits non-zero on an input without a mapped.sam or when no read could be used."""
+    import logging
+    from . import squiggle as squiggle_mod
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    try:
+        report = squiggle_mod.squiggle_command(args)
+    except ValueError as e:
+        sys.exit("squiggle: %s" % e)
+    print("squiggle: %d of %d reads used, %d bases and %d samples in %d tiles; %d events on the genome; wrote %s"
+          % (report["reads"]["used"], report["reads"]["total"], report["bases"], report["samples"], report["tiles"], report["events"],
+             ", ".join(report["files"])))
+    if report["reads"]["used"] == 0:
+        sys.exit("squiggle: no read of %s could be used (%s)" % (report["sam"], report["reads"]["dropped"]))
+    return report
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -557,6 +577,34 @@ def build_parser():
     dm.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one search call, MiB.")
     dm.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     dm.set_defaults(func=demux)
+    sq = subparsers.add_parser("squiggle", description="Put the reads' current levels on the genome: the samples of every called base "
+                               "reduced to one level and the levels summed per position and strand on the GPU; with a control sample, "
+                               "Welch's t per position (sample-compare detection of modified bases)",
+                               help="Signal levels per genome position, sample comparison, k-mer level table.")
+    sq.add_argument("-i", "--input", required=True, help="Output folder of `map --cigar` (its mapped.sam is read), or a SAM file.")
+    sq.add_argument("-s", "--signal", required=True, help="Output folder of `call` (its raw/ is read), or a folder of .signal files.")
+    sq.add_argument("-g", "--genome", required=True, help="The genome FASTA the reads were mapped to.")
+    sq.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder path")
+    sq.add_argument("-o", "--output", required=True, help="Folder levels.tsv, squiggle_report.json and the optional outputs are written to.")
+    sq.add_argument("--control", default=None, help="The control sample's `map --cigar` folder or SAM file: compare.tsv is written.")
+    sq.add_argument("--control-signal", dest="control_signal", default=None, help="The control sample's `call` folder or folder of .signal files.")
+    sq.add_argument("--normalize", default="mad", choices=["mad", "none"],
+                    help="mad: per read, (x - median) / MAD in 1/256 units; none: the samples as they are, rounded.")
+    sq.add_argument("--min-events", dest="min_events", type=int, default=5,
+                    help="Fewest events both samples must have at a position and strand for it to be compared (at least 2).")
+    sq.add_argument("--kmer", type=int, default=0, help="Also write kmer_levels.tsv, the level table of the genome K-mers (1 to 10).")
+    sq.add_argument("--events", action="store_true", help="Also write events/<read>.tsv, one row per base.")
+    sq.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
+    sq.add_argument("-b", "--batch_size", type=int, default=1100, help="Windows per engine batch.")
+    sq.add_argument("--band", type=int, default=256, help="First half-width of the frame alignment's band, in CTC states; 0: the full table.")
+    sq.add_argument("--max-band", dest="max_band", type=int, default=8192,
+                    help="Largest half-width the doubling may reach before a read is given up (0: unbounded).")
+    sq.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one call of any stage, MiB.")
+    sq.add_argument("--dtype", default="fp32", choices=["fp32", "fp16", "fp16-w2", "fp32-split"], help="Engine arithmetic.")
+    sq.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    sq.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
+                    help="Use seeded synthetic weights when the model folder has no checkpoint data.")
+    sq.set_defaults(func=squiggle)
     return parser
 
 

@@ -414,8 +414,8 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *
  * Caller's memory.  This holds for every call below that takes a workspace, a tape or a device output buffer from its caller --
  * chiron_ctc_loss, chiron_rnn_train_forward / _backward, chiron_cnn_train_forward / _backward, chiron_align_pairs,
- * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows and
- * chiron_pileup; their own comments say "uninitialised" or name the size function and mean this:
+ * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
+ * chiron_pileup and chiron_signal_levels; their own comments say "uninitialised" or name the size function and mean this:
  *   - workspace, tape and output buffers may hold anything on entry: the results do not depend on it (the library clears what it
  *     needs cleared, on the call's stream);
  *   - every element of every output is written, the rows and frames that carry no result included (frames past seq_len, skipped and
@@ -423,7 +423,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *     chiron_cnn_train_forward (only the statistics' slots are written) and a failed pair's slice of chiron_align_trace's ops_out;
  *   - nothing outside the bytes that the call's *_workspace_size / *_train_sizes function names, and outside the outputs' own
  *     extents, is read or written: a caller may pack other data right behind a workspace of exactly that size.
- * tests/test_gpu_workspace.py holds every one of these calls to the three parts.                                                 */
+ * tests/test_gpu_workspace.py holds every one of these calls to the three parts (chiron_signal_levels: tests/test_gpu_squiggle.py). */
 #define CHIRON_CTC_WANT_GRAD 1u
 #define CHIRON_CTC_TRUSTED 2u   /* chiron_ctc_loss: the caller has checked seq_len / labels / label_len: no read-back, no sync */
 #define CHIRON_CTC_MAX_T 8192
@@ -925,6 +925,53 @@ chiron_status chiron_pileup(int32_t device_id, const uint8_t* codes, const int64
                             const int64_t* pos, int64_t alignments, int64_t g0, int64_t g1, const uint8_t* ref_codes, int32_t min_depth,
                             uint32_t flags, int32_t* counts_out, int32_t* depth_out, uint8_t* call_out, int64_t* clipped_out,
                             void* workspace, void* stream);
+
+/* Signal levels: the mean current every read spent on each of its bases, and the sums of those levels per bin -- a genome position
+ * and strand, or a k-mer; what a bin means is the caller's business.  Read r has S_r = sample_off[r+1] - sample_off[r] int16 samples,
+ * samples[sample_off[r] ..), and L_r = base_off[r+1] - base_off[r] bases in SIGNAL order.  Its L_r + 1 entries of `start` are
+ * start[base_off[r] + r .. base_off[r+1] + r]: relative to the read's first sample, never decreasing, inside 0 .. S_r; `start` holds
+ * base_off[reads] + reads entries in all.  Base n of the read owns the samples start[n] .. start[n+1]); the samples before start[0]
+ * belong to nobody.  Its L_r entries of `bin` are bin[base_off[r] ..): -1, or a bin 0 .. bins - 1.
+ *
+ * Per base with c = start[n+1] - start[n] > 0 samples of sum s (64-bit):
+ *   level = floor((2 s + c) / (2 c))      the mean rounded to nearest, halves up; floor division, not C's truncation: the samples
+ *                                         [-1, -2] give -1 and [1, 2] give 2
+ * It goes to level_out[base_off[r] - base_off[0] + n] whatever the bin, and when the base's bin b is not -1 the planes get
+ *   events[b] += 1,  dwell[b] += c,  sum[b] += level,  sq[b] += level * level.
+ * A base with c = 0 gets CHIRON_SIGNAL_EMPTY and adds nothing.  Every sum is an integer sum, so the result is a property of the
+ * inputs; with at most CHIRON_SIGNAL_MAX_SAMPLES samples a call |sum| <= 2^46 and sq <= 2^61, inside int64.
+ *
+ * signal_kernel (csrc/signal.hip): flat over bases, a base a lane, from a 16-byte record per base that the host's checking walk
+ * writes (csrc/signal_pack.h: first sample, count, bin).  Chunks of 64 consecutive bases are dealt to the launch's waves
+ * round-robin, CHIRON_SIGNAL_THREADS / 64 waves a workgroup, at most CHIRON_SIGNAL_MAX_GROUPS workgroups.  A wave stages its
+ * chunk's run of samples through 2 KiB of LDS, 1024 samples at a time with 16-byte loads, every sample once, and each lane sums its
+ * span out of LDS.  Levels leave by plain stores, the planes get relaxed agent-scope 64-bit atomic adds.  Every offset is 64-bit.
+ *
+ * Workspace (device memory), each part rounded up to 256 bytes: 16 bytes of record a base, 2 bytes a sample, with want_levels != 0
+ * 4 bytes a base, and CHIRON_SIGNAL_PLANES int64 planes of `bins`.  `reads` takes no room.  Larger values of any argument are fine.
+ * Host-only.  CHIRON_ERR_INVALID: a negative argument.  CHIRON_ERR_OVERFLOW: samples > CHIRON_SIGNAL_MAX_SAMPLES, bases > 2^31 - 1,
+ * bins > CHIRON_SIGNAL_MAX_BINS.                                                                                                   */
+#define CHIRON_SIGNAL_PLANES 4            /* int64, PLANAR [4][bins]: 0 events, 1 dwell, 2 sum of levels, 3 sum of squared levels */
+#define CHIRON_SIGNAL_EMPTY INT32_MIN     /* level_out of a base with no sample */
+#define CHIRON_SIGNAL_MAX_SAMPLES 0x7FFFFFFF   /* samples of one call */
+#define CHIRON_SIGNAL_MAX_BINS (1 << 28)
+#define CHIRON_SIGNAL_THREADS 256
+#define CHIRON_SIGNAL_MAX_GROUPS 2048
+chiron_status chiron_signal_workspace_size(int64_t reads, int64_t samples, int64_t bases, int64_t bins, int32_t want_levels, size_t* bytes);
+
+/* The levels and planes of `reads` reads in one launch.  samples, sample_off (int64 [reads + 1]), start, base_off (int64 [reads + 1])
+ * and bin are HOST memory, the offsets non-negative and non-decreasing.  Outputs, HOST memory: planes_out int64
+ * [CHIRON_SIGNAL_PLANES][bins], PLANAR (may be NULL only when bins == 0); level_out int32 [base_off[reads] - base_off[0]] (may be
+ * NULL: the levels are then neither kept nor copied).  workspace: device memory on device_id of
+ * chiron_signal_workspace_size(reads, the call's samples, the call's bases, bins, level_out wanted) bytes ("Caller's memory" above).
+ * flags: 0 (reserved).  Copies the records and the samples in, clears the planes, runs signal_kernel on `stream` (a hipStream_t;
+ * NULL = the null stream) and synchronises it before returning.  CHIRON_ERR_INVALID: unknown flags, a negative count, a null array
+ * that is needed, a negative or decreasing offset, a start entry that decreases or leaves 0 .. S_r, a bin below -1 or at or above
+ * bins.  CHIRON_ERR_OVERFLOW: as the size function.  All of it before anything is copied or launched.  reads == 0 (or no base at
+ * all) with bins > 0 clears and returns the planes; with bins == 0 as well the call touches no device.                          */
+chiron_status chiron_signal_levels(int32_t device_id, const int16_t* samples, const int64_t* sample_off, const int32_t* start,
+                                   const int64_t* base_off, const int32_t* bin, int64_t reads, int64_t bins, uint32_t flags,
+                                   int64_t* planes_out, int32_t* level_out, void* workspace, void* stream);
 
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
