@@ -29,6 +29,7 @@ CTC_MAX_T, CTC_MAX_LABEL = 8192, 1 << 24
 ALIGN_MAX_LEN, ALIGN_BAND0, ALIGN_THREADS, ALIGN_LDS_SLOTS, ALIGN_MAX_GROUPS = 1 << 17, 256, 256, 4096, 2048
 INFIX_MAX_READ, INFIX_MAX_WINDOW, INFIX_BAND0, INFIX_THREADS, INFIX_LDS_SLOTS, INFIX_MAX_GROUPS = 1 << 17, (1 << 20) - 1, 256, 256, 4096, 2048
 SEED_K, SEED_BIN, SEED_THREADS, SEED_MAX_GROUPS, SEED_MAX_GENOME = 15, 256, 256, 2048, (1 << 31) - (1 << 18)
+SEED_MAX_CANDIDATES = 8
 LABEL_MAX_FRAMES, LABEL_MAX_BASES, LABEL_THREADS, LABEL_LDS_SLOTS, LABEL_MAX_GROUPS = 1 << 24, 1 << 22, 256, 4096, 1024
 SCORE_MAX_FRAMES, SCORE_MAX_LABEL, SCORE_THREADS, SCORE_MAX_GROUPS = 4096, 127, 256, 2048
 DEMUX_MAX_PATTERN, DEMUX_MAX_WINDOW, DEMUX_MAX_PATTERNS, DEMUX_THREADS, DEMUX_MAX_GROUPS, DEMUX_NONE = 64, 4096, 65536, 256, 2048, 0x7FFFFFFF
@@ -160,6 +161,9 @@ SYMBOLS = [
     ("chiron_seed_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     ("chiron_seed_reads", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_seed_candidates_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("chiron_seed_candidates", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("chiron_ctc_align_workspace_size", C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("chiron_ctc_align", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

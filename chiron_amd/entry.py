@@ -203,7 +203,8 @@ def assess(args):
         if args.reference:
             raise ValueError("assess: give the references with -r or a genome with -g, not both")
         report = map_mod.assess_genome(args.input, args.genome, workspace_mb=args.workspace_mb, device_id=args.device, profile=args.profile,
-                                       seed=getattr(args, "seed", DEFAULT_SEED))
+                                       seed=getattr(args, "seed", DEFAULT_SEED), candidates=getattr(args, "candidates", 1),
+                                       second_ratio=getattr(args, "second_ratio", 0.5))
     else:
         report = assess_mod.assess(args.input, args.reference, strand=args.strand, device_id=args.device, profile=args.profile,
                                    workspace_mb=args.workspace_mb)
@@ -226,10 +227,14 @@ def map_reads(args):
     non-zero when no read mapped."""
     from . import map as map_mod
     report = map_mod.map_command(args.input, args.genome, args.output, min_votes=args.min_votes, max_occ=args.max_occ, band=args.band,
-                                 workspace_mb=args.workspace_mb, device_id=args.device, cigar=args.cigar, seed=getattr(args, "seed", DEFAULT_SEED))
+                                 workspace_mb=args.workspace_mb, device_id=args.device, cigar=args.cigar, seed=getattr(args, "seed", DEFAULT_SEED),
+                                 candidates=getattr(args, "candidates", 1), second_ratio=getattr(args, "second_ratio", 0.5))
     t = report["totals"]
     print("map: %d reads; %d mapped, %d unmapped, %d at a window edge; identity of the mapped reads %.4f"
           % (t["reads"], t["mapped"], t["unmapped"], t["edge"], t["identity"]))
+    if "mapq0" in report:
+        print("map: up to %d candidates a read; mapq 0: %d reads, 1 .. 59: %d, 60: %d; %d won by a pick other than the first"
+              % (report["candidates"], report["mapq0"], report["mapq1_59"], report["mapq60"], report["won_by_later_pick"]))
     for name in report["unmapped"]:
         print("map: read %s did not map" % name, file=sys.stderr)
     if t["mapped"] == 0:
@@ -244,7 +249,7 @@ def pileup(args):
     from . import pileup as pileup_mod
     try:
         report = pileup_mod.pileup_command(args.input, args.genome, args.output, min_depth=args.min_depth, workspace_mb=args.workspace_mb,
-                                           device_id=args.device)
+                                           device_id=args.device, min_mapq=getattr(args, "min_mapq", 0))
     except ValueError as e:
         sys.exit("pileup: %s" % e)
     t = report["totals"]
@@ -290,8 +295,11 @@ def label(args):
         from . import assess as assess_mod, map as map_mod
         if args.reference:
             raise ValueError("label: give the references with -r or a genome with -g, not both")
+        seed = getattr(args, "seed", DEFAULT_SEED)
         mapped = map_mod.map_reads(assess_mod.load_reads(args.input), map_mod.load_genome(args.genome), device_id=args.device,
-                                   seeder=map_mod.seeder_of(getattr(args, "seed", DEFAULT_SEED), device_id=args.device))
+                                   seeder=map_mod.seeder_of(seed, device_id=args.device), candidates=getattr(args, "candidates", 1),
+                                   second_ratio=getattr(args, "second_ratio", 0.5),
+                                   top_seeder=map_mod.top_seeder_of(seed, device_id=args.device))
         args.reference = path.join(args.output, "reference")
         map_mod.write_references(args.reference, mapped["references"])
     report = label_mod.label(args)
@@ -470,6 +478,12 @@ def build_parser():
     a.add_argument("--seed", default=DEFAULT_SEED, choices=["gpu", "host"],
                    help="Where the k-mer votes of the mapping are counted: on the GPU, or per read in numpy on the host (the reference; "
                         "the results are the same).")
+    a.add_argument("--candidates", type=int, default=1,
+                    help="Seeding candidates a read (1 to 8).  Above 1 the best candidates are all aligned, the best alignment wins and "
+                         "the read gets a mapping quality (an ordering, not a calibrated probability; not tuned on real reads).")
+    a.add_argument("--second-ratio", dest="second_ratio", type=float, default=0.5,
+                    help="With --candidates above 1: a candidate is aligned when it has at least this share of the best one's votes "
+                         "(not tuned on real reads).")
     a.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one traceback batch, MiB.")
     a.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     a.set_defaults(func=assess)
@@ -486,6 +500,12 @@ def build_parser():
     lb.add_argument("--seed", default=DEFAULT_SEED, choices=["gpu", "host"],
                     help="Where the k-mer votes of the mapping are counted: on the GPU, or per read in numpy on the host (the reference; "
                          "the results are the same).")
+    lb.add_argument("--candidates", type=int, default=1,
+                    help="Seeding candidates a read (1 to 8).  Above 1 the best candidates are all aligned, the best alignment wins and "
+                         "the read gets a mapping quality (an ordering, not a calibrated probability; not tuned on real reads).")
+    lb.add_argument("--second-ratio", dest="second_ratio", type=float, default=0.5,
+                    help="With --candidates above 1: a candidate is aligned when it has at least this share of the best one's votes "
+                         "(not tuned on real reads).")
     lb.add_argument("-o", "--output", required=True, help="Folder the .signal/.label pairs and label_report.json are written to.")
     lb.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder path")
     lb.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
@@ -512,6 +532,12 @@ def build_parser():
     mp.add_argument("--seed", default=DEFAULT_SEED, choices=["gpu", "host"],
                     help="Where the k-mer votes of the mapping are counted: on the GPU, or per read in numpy on the host (the reference; "
                          "the results are the same).")
+    mp.add_argument("--candidates", type=int, default=1,
+                    help="Seeding candidates a read (1 to 8).  Above 1 the best candidates are all aligned, the best alignment wins and "
+                         "the read gets a mapping quality (an ordering, not a calibrated probability; not tuned on real reads).")
+    mp.add_argument("--second-ratio", dest="second_ratio", type=float, default=0.5,
+                    help="With --candidates above 1: a candidate is aligned when it has at least this share of the best one's votes "
+                         "(not tuned on real reads).")
     mp.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one seeding or alignment batch, MiB.")
     mp.add_argument("--cigar", action="store_true",
                     help="Also trace every mapped read against the stretch it covers, in genome orientation: mapped.paf gains a cg:Z: "
@@ -525,6 +551,8 @@ def build_parser():
     pu.add_argument("-g", "--genome", required=True, help="The genome FASTA the reads were mapped to.")
     pu.add_argument("-o", "--output", required=True, help="Folder consensus.fasta, variants.tsv and pileup_report.json are written to.")
     pu.add_argument("--min-depth", dest="min_depth", type=int, default=3, help="Positions covered by fewer alignments keep the genome's base.")
+    pu.add_argument("--min-mapq", dest="min_mapq", type=int, default=0,
+                    help="Drop alignments whose MAPQ is below this (`map --candidates` writes one; 255, not available, always passes).")
     pu.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one genome tile, MiB.")
     pu.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     pu.set_defaults(func=pileup)
@@ -543,6 +571,8 @@ def build_parser():
                     help="A variant is eligible when its summed log-likelihood ratio exceeds this (not tuned on real reads).")
     po.add_argument("--min-reads", dest="min_reads", type=int, default=3, help="Fewest reads that must have scored a variant.")
     po.add_argument("--min-depth", dest="min_depth", type=int, default=3, help="As for `pileup`: the vote's own depth floor (reported only).")
+    po.add_argument("--min-mapq", dest="min_mapq", type=int, default=0,
+                    help="Drop alignments whose MAPQ is below this (`map --candidates` writes one; 255, not available, always passes).")
     po.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
     po.add_argument("-b", "--batch_size", type=int, default=1100, help="Windows per engine batch.")
     po.add_argument("--band", type=int, default=256, help="First half-width of the frame alignment's band, in CTC states; 0: the full table.")
@@ -592,6 +622,8 @@ def build_parser():
                     help="mad: per read, (x - median) / MAD in 1/256 units; none: the samples as they are, rounded.")
     sq.add_argument("--min-events", dest="min_events", type=int, default=5,
                     help="Fewest events both samples must have at a position and strand for it to be compared (at least 2).")
+    sq.add_argument("--min-mapq", dest="min_mapq", type=int, default=0,
+                    help="Drop alignments whose MAPQ is below this (`map --candidates` writes one; 255, not available, always passes).")
     sq.add_argument("--kmer", type=int, default=0, help="Also write kmer_levels.tsv, the level table of the genome K-mers (1 to 10).")
     sq.add_argument("--events", action="store_true", help="Also write events/<read>.tsv, one row per base.")
     sq.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")

@@ -17,8 +17,13 @@ rule on the GPU, equal to it field for field, and what the commands run unless t
            delta // 256 (floor).  The score of a bin beta that holds a hit is count(beta) + count(beta + 1); the best score wins,
            ties to forward before reverse, then to the smaller beta.  The candidate delta* is the lower median of the hits of the
            winning two bins, ordered by (delta, g); the contig is the one that holds that hit's g.  Below min_votes the read is
-           unmapped.  votes_second is the best score of the other strand or of a bin more than n // 256 + 2 away: reported,
-           never acted on (it is no mapping quality -- the two scores count seeds, not alignments).
+           unmapped.  votes_second is the best score of the other strand or of a bin more than n // 256 + 2 away: with one
+           candidate a read it is reported, never acted on (it is no mapping quality -- the two scores count seeds, not
+           alignments).
+  top-K    `vote_top` (on the GPU `vote_reads_top`, chiron_seed_candidates) picks up to K (strand, bin) pairs a read, each
+           suppressing its neighbourhood; map_reads(candidates=K) aligns those with enough votes in the same launches, keeps the
+           best alignment and derives a mapping quality from the two best edit distances: an ordering, not a calibrated
+           probability, with defaults that are not tuned on real reads.  K = 1, the default, is the single-candidate path.
   window   [delta* - slack, delta* + n + slack) clipped to the contig, slack = max(256, n // 8).
   edge     a match that touches a window edge which is not a contig edge (s = 0, or e = m while the contig goes on) may continue
            outside: the read's slack doubles and it is aligned again in a follow-up launch, at most three times; then `edge`.
@@ -36,6 +41,7 @@ BIN = 256
 SEPARATOR = K                           # code-4 bases between two contigs
 MAX_WIDENINGS = 3
 MIN_VOTES, MAX_OCC = 4, 64
+MAPQ_MAX = 60                           # the mapq of a read with one mapped candidate; 255 in a file is "not available"
 THREADS = _lib.INFIX_THREADS
 LDS_SLOTS = _lib.INFIX_LDS_SLOTS
 BAND0 = _lib.INFIX_BAND0
@@ -214,6 +220,38 @@ def vote(index, read_codes, k=K):
     return out
 
 
+def vote_top(index, read_codes, max_cand, min_score=1, k=K):
+    """Up to max_cand seeding candidates of one read, best first: the definition of chiron_seed_candidates.  Bins and scores are
+    those of `vote` (bin_scores on both strands).  Greedily: among the (strand, bin) pairs that hold a hit and are not
+    suppressed, the largest score, ties to forward, then to the smaller bin; stop when nothing is left, when that score is below
+    min_score, or after max_cand picks.  A pick at bin beta suppresses the bins b of its own strand with |b - beta| <= n // BIN + 2
+    (the complement of `vote`'s "far"), and its (delta, g) is `vote`'s lower median over the hits of bins beta and beta + 1; the
+    radius is at least 2, so no two picks share a bin.  Pick 0 is `vote`'s candidate and pick 1's votes are its votes_second.
+    -> [dict(votes, strand, delta, g)] in pick order."""
+    n = len(read_codes)
+    reach = n // BIN + 2
+    per = []
+    for strand, codes in (("forward", read_codes), ("reverse", assess.reverse_complement(read_codes))):
+        delta, g = hits(index, codes, k)
+        bins, score = bin_scores(delta) if len(delta) else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+        per.append((strand, delta, g, bins, score.astype(np.int64), np.ones(len(bins), bool)))
+    picks = []
+    while len(picks) < max_cand:
+        best = [int(np.where(p[5], p[4], 0).max()) if len(p[4]) else 0 for p in per]     # a bin that holds a hit scores at least 1
+        w = 1 if best[1] > best[0] else 0                                                 # forward wins a tie
+        if best[w] < max(min_score, 1):
+            break
+        strand, delta, g, bins, score, free = per[w]
+        beta = int(bins[int(np.argmax(np.where(free, score, 0)))])                        # the first maximum: the smaller beta
+        free &= np.abs(bins - beta) > reach
+        b = delta // BIN
+        sel = np.nonzero((b == beta) | (b == beta + 1))[0]
+        order = np.lexsort((g[sel], delta[sel]))
+        mid = sel[order[(len(sel) - 1) // 2]]
+        picks.append({"votes": best[w], "strand": strand, "delta": int(delta[mid]), "g": int(g[mid])})
+    return picks
+
+
 # ----------------------------------------------------------------------------------------------------------------------------
 # the votes on the GPU
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -225,12 +263,19 @@ def seed_workspace_size(n_index, genome_len, reads, max_read, total_bases):
     return _lib.sized("chiron_seed_workspace_size", n_index, genome_len, reads, max_read, total_bases)
 
 
-def plan_seed_batches(read_lens, n_index, genome_len, budget_bytes):
-    """Consecutive reads grouped so that each group's workspace stays within the budget (a single read always forms a group)."""
+def seed_candidates_workspace_size(n_index, genome_len, reads, max_read, total_bases, max_cand):
+    return _lib.sized("chiron_seed_candidates_workspace_size", n_index, genome_len, reads, max_read, total_bases, max_cand)
+
+
+def plan_seed_batches(read_lens, n_index, genome_len, budget_bytes, max_cand=None):
+    """Consecutive reads grouped so that each group's workspace stays within the budget (a single read always forms a group).
+    max_cand: plan for chiron_seed_candidates with that many candidates instead of chiron_seed_reads."""
+    def size(*args):
+        return seed_workspace_size(*args) if max_cand is None else seed_candidates_workspace_size(*args, max_cand)
     batches, cur, mr, total = [], [], 0, 0
     for i, n in enumerate(read_lens):
         nr, nt = max(mr, n), total + n
-        if cur and seed_workspace_size(n_index, genome_len, len(cur) + 1, nr, nt) > budget_bytes:
+        if cur and size(n_index, genome_len, len(cur) + 1, nr, nt) > budget_bytes:
             batches.append(cur)
             cur, nr, nt = [], n, n
         cur.append(i)
@@ -277,6 +322,43 @@ def vote_reads(index, reads, workspace_mb=4096, device_id=0):
     return out
 
 
+def seed_candidates(idx_val, idx_pos, genome_len, reads, max_cand, min_score=1, device_id=0):
+    """One call of chiron_seed_candidates; operands as for seed_reads.  -> (count int32 [reads]; votes, strand int32 and delta, g
+    int64, each [reads, max_cand], zeros from a read's count on)."""
+    count = len(reads)
+    lens = np.array([len(r) for r in reads], dtype=np.int64)
+    read_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    codes = np.ascontiguousarray(np.concatenate(list(reads) + [np.zeros(1, np.uint8)]))
+    res = [np.zeros(count, dtype=np.int32)] + [np.zeros((count, max_cand), dtype=t) for t in (np.int32, np.int32, np.int64, np.int64)]
+    if count == 0:
+        return res
+    lib, ws, stream = _lib.device_workspace(
+        lambda: seed_candidates_workspace_size(len(idx_val), genome_len, count, int(lens.max()), int(lens.sum()), max_cand),
+        device_id, "map.vote_reads_top", "seeding")
+    _lib.check(lib.chiron_seed_candidates(device_id, idx_val.ctypes.data, idx_pos.ctypes.data, len(idx_val), genome_len, codes.ctypes.data,
+                                          read_off.ctypes.data, count, max_cand, min_score, 0, *[r.ctypes.data for r in res],
+                                          ws.data_ptr(), stream))
+    del ws
+    return res
+
+
+def vote_reads_top(index, reads, max_cand, min_score=1, workspace_mb=4096, device_id=0):
+    """`vote_top` of every read, on the GPU: [vote_top(index, r, max_cand, min_score) for r in reads], field for field; batches
+    as in vote_reads, planned with chiron_seed_candidates_workspace_size."""
+    import torch  # noqa: F401  before the library loads: torch's ROCm runtime has to come up first (_lib.py)
+    idx_val, idx_pos = index
+    genome_len = int(idx_pos.max()) + K if len(idx_pos) else 0
+    reads = [assess.encode(r) for r in reads]
+    batches = plan_seed_batches([len(r) for r in reads], len(idx_val), genome_len, int(workspace_mb * (1 << 20)), max_cand)
+    val32, pos32 = np.ascontiguousarray(idx_val, dtype=np.uint32), np.ascontiguousarray(idx_pos, dtype=np.int32)
+    out = []
+    for batch in batches:
+        count, votes, strand, delta, g = seed_candidates(val32, pos32, genome_len, [reads[i] for i in batch], max_cand, min_score, device_id)
+        for c, v, w, d, at in zip(count.tolist(), votes.tolist(), strand.tolist(), delta.tolist(), g.tolist()):
+            out.append([{"votes": v[k], "strand": "reverse" if w[k] else "forward", "delta": d[k], "g": at[k]} for k in range(c)])
+    return out
+
+
 def seeder_of(seed, workspace_mb=4096, device_id=0):
     """The `seeder` of map_reads for a command's --seed: None (the per-read host `vote`) for "host", vote_reads for "gpu"."""
     if seed not in SEEDS:
@@ -284,6 +366,15 @@ def seeder_of(seed, workspace_mb=4096, device_id=0):
     if seed == "host":
         return None
     return lambda index, reads: vote_reads(index, reads, workspace_mb, device_id)
+
+
+def top_seeder_of(seed, workspace_mb=4096, device_id=0):
+    """The `top_seeder` of map_reads for a command's --seed: None (the per-read host `vote_top`) or vote_reads_top."""
+    if seed not in SEEDS:
+        raise ValueError("seed must be one of %s, not %r" % (", ".join(SEEDS), seed))
+    if seed == "host":
+        return None
+    return lambda index, reads, max_cand, min_score: vote_reads_top(index, reads, max_cand, min_score, workspace_mb, device_id)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -298,12 +389,57 @@ def window_of(genome, contig, delta, n, slack):
     return lo, hi
 
 
+def mapq_of(edits):
+    """The mapping quality of a read from the edit distances of its mapped candidates: 60 with one; with E1 <= E2 the two
+    smallest, min(60, 600 * (E2 - E1) // max(E2, 1)); 0 with none.  An ordering, not a calibrated probability."""
+    if not edits:
+        return 0
+    if len(edits) == 1:
+        return MAPQ_MAX
+    e1, e2 = sorted(edits)[:2]
+    return min(MAPQ_MAX, 600 * (e2 - e1) // max(e2, 1))
+
+
+def candidates_of(picks, min_votes, second_ratio):
+    """The picks of a read (vote_top order) that are aligned: votes >= min_votes and >= ceil(second_ratio * votes of pick 0)."""
+    if not picks:
+        return []
+    floor = int(np.ceil(second_ratio * picks[0]["votes"]))
+    return [(rank, p) for rank, p in enumerate(picks) if p["votes"] >= min_votes and p["votes"] >= floor]
+
+
+def choose(cands):
+    """cands: a read's aligned candidates in rank order, dicts with rank, contig, strand, start, end, edit, match, status.  Drops
+    as a duplicate every candidate whose interval overlaps that of an earlier-ranked kept one on the same contig and strand;
+    -> (the primary: the mapped one with the smallest (edit, -match, rank), or None; mapq; the second-smallest edit among the
+    mapped ones, or None)."""
+    kept = []
+    for c in cands:
+        if not any(k["contig"] == c["contig"] and k["strand"] == c["strand"] and c["start"] < k["end"] and k["start"] < c["end"] for k in kept):
+            kept.append(c)
+    good = sorted((c for c in kept if c["status"] == "mapped"), key=lambda c: (c["edit"], -c["match"], c["rank"]))
+    if not good:
+        return None, 0, None
+    return good[0], mapq_of([c["edit"] for c in good]), good[1]["edit"] if len(good) > 1 else None
+
+
 def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0, aligner=None,
-              seeds=None, index=None, seeder=None):
+              seeds=None, index=None, seeder=None, candidates=1, second_ratio=0.5, top_seeder=None):
     """Map {name: sequence} against a Genome.  aligner(reads, windows, band0) -> INFIX_DTYPE rows replaces the GPU kernel
     (the tests' reference pipeline); seeds {name: dict(strand, delta, contig)} replaces the voting for those reads (a test
     hook); seeder(index, [codes]) -> [vote dicts] replaces the per-read host `vote` for the others (seeder_of).  -> dict(reads=[per-read records, name order], references={name: cut-out in the read's orientation}, totals,
-    unmapped=[names])."""
+    unmapped=[names]).
+
+    candidates > 1: every read's picks of top_seeder(index, [codes], candidates, min_score) -> [pick lists] (top_seeder_of; None
+    is the per-read host vote_top) that pass candidates_of go through the window and widening loop together, in the same
+    launches, and `choose` names the primary.  The record is the primary's (pick 0's when none mapped) and gains mapq,
+    candidates (the number aligned), edit_second and seed_rank; its votes are pick 0's and its votes_second pick 1's (0 below
+    min_votes).  A read without a pick of min_votes gets the single-candidate record, from `seeder`.  The result gains
+    `ambiguity`: the reads at mapq 0, 1 .. 59 and 60 and those won by a pick other than 0."""
+    if candidates < 1 or candidates > _lib.SEED_MAX_CANDIDATES:
+        raise ValueError("candidates must be 1 .. %d, not %r" % (_lib.SEED_MAX_CANDIDATES, candidates))
+    if not 0.0 <= second_ratio <= 1.0:
+        raise ValueError("second_ratio must be within 0 .. 1, not %r" % (second_ratio,))
     if aligner is None:
         def aligner(rs, ws, band0):
             return align_in_batches(rs, ws, band0, workspace_mb, device_id)
@@ -312,14 +448,33 @@ def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, w
     recs, todo = {}, []
     coded = {name: assess.encode(reads[name]) for name in sorted(reads)}
     voting = [name for name in coded if seeds is None or name not in seeds]
+    picked = {}
+    if candidates > 1:
+        min_score = max(1, min_votes)
+        tops = (top_seeder(index, [coded[name] for name in voting], candidates, min_score) if top_seeder is not None else
+                [vote_top(index, coded[name], candidates, min_score) for name in voting])
+        picked = {name: picks for name, picks in zip(voting, tops) if picks}
+        voting = [name for name in voting if name not in picked]
     voted = dict(zip(voting, seeder(index, [coded[name] for name in voting]) if seeder is not None else
                      (vote(index, coded[name]) for name in voting)))
+    several = {}                                                              # name -> its candidates' records, rank order
     for name, codes in coded.items():
         n = len(codes)
         rec = {"name": name, "read_len": n, "contig": None, "start": None, "end": None, "strand": None, "edit": None, "match": None,
                "mismatch": None, "insertion": None, "deletion": None, "identity": None, "votes": 0, "votes_second": 0, "band": None,
                "widenings": 0, "status": "unmapped"}
         recs[name] = rec
+        if name in picked:
+            picks = picked[name]
+            rec["votes"], rec["votes_second"] = picks[0]["votes"], picks[1]["votes"] if len(picks) > 1 else 0
+            several[name] = []
+            for rank, v in candidates_of(picks, min_votes, second_ratio):
+                contig = genome.contig_of(v["g"])
+                sub = dict(rec, strand=v["strand"], contig=genome.names[contig], rank=rank)
+                several[name].append(sub)
+                todo.append({"rec": sub, "key": (name, rank), "codes": codes if v["strand"] == "forward" else assess.reverse_complement(codes),
+                             "delta": v["delta"], "contig": contig, "slack": max(BIN, n // 8)})
+            continue
         if seeds is not None and name in seeds:
             sd = seeds[name]
             strand, delta, contig = sd["strand"], int(sd["delta"]), int(sd["contig"])
@@ -330,7 +485,7 @@ def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, w
                 continue
             strand, delta, contig = v["strand"], v["delta"], genome.contig_of(v["g"])
         rec["strand"], rec["contig"] = strand, genome.names[contig]
-        todo.append({"rec": rec, "codes": codes if strand == "forward" else assess.reverse_complement(codes), "delta": delta,
+        todo.append({"rec": rec, "key": name, "codes": codes if strand == "forward" else assess.reverse_complement(codes), "delta": delta,
                      "contig": contig, "slack": max(BIN, n // 8)})
     references = {}
     while todo:
@@ -355,16 +510,37 @@ def map_reads(reads, genome, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, w
             rec.update(assess.rates(M, x, i, d))
             if not touches:
                 cut = genome.codes[lo + s:lo + e]
-                references[rec["name"]] = decode(cut if rec["strand"] == "forward" else assess.reverse_complement(cut))
+                references[t["key"]] = decode(cut if rec["strand"] == "forward" else assess.reverse_complement(cut))
         todo = again
+    if candidates > 1:
+        for name, rec in recs.items():
+            cands = several.get(name)
+            if cands is None:                                                 # a single-candidate record: given seeds, or no pick
+                rec.update({"mapq": MAPQ_MAX if rec["status"] == "mapped" else 0, "candidates": int(rec["status"] != "unmapped"),
+                            "edit_second": None, "seed_rank": 0 if rec["status"] != "unmapped" else None})
+                continue
+            primary, mapq, second = choose(cands)
+            shown = primary if primary is not None else cands[0] if cands else None
+            if shown is not None:
+                rec.update({key: shown[key] for key in shown if key not in ("rank", "votes", "votes_second")})
+            rec.update({"mapq": mapq, "candidates": len(cands), "edit_second": second, "seed_rank": shown["rank"] if shown is not None else None})
+        chosen = {name: (name, rec["seed_rank"]) for name, rec in recs.items() if name in several}
+        references = {key if not isinstance(key, tuple) else key[0]: seq for key, seq in references.items()
+                      if not isinstance(key, tuple) or (chosen[key[0]] == key and recs[key[0]]["status"] == "mapped")}
     per_read = [recs[name] for name in sorted(recs)]
     totals = {st: sum(1 for r in per_read if r["status"] == st) for st in ("mapped", "unmapped", "edge")}
     totals["reads"] = len(per_read)
     for key in ("edit", "match", "mismatch", "insertion", "deletion"):
         totals[key] = int(sum(r[key] for r in per_read if r["status"] == "mapped"))
     totals.update(assess.rates(totals["match"], totals["mismatch"], totals["insertion"], totals["deletion"]))
-    return {"reads": per_read, "references": references, "totals": totals,
-            "unmapped": [r["name"] for r in per_read if r["status"] == "unmapped"]}
+    result = {"reads": per_read, "references": references, "totals": totals,
+              "unmapped": [r["name"] for r in per_read if r["status"] == "unmapped"]}
+    if candidates > 1:
+        result["ambiguity"] = {"mapq0": sum(1 for r in per_read if r["mapq"] == 0),
+                               "mapq1_59": sum(1 for r in per_read if 0 < r["mapq"] < MAPQ_MAX),
+                               "mapq60": sum(1 for r in per_read if r["mapq"] == MAPQ_MAX),
+                               "won_by_later_pick": sum(1 for r in per_read if r["seed_rank"])}
+    return result
 
 
 def add_cigars(result, reads, genome, workspace_mb=4096, device_id=0, tracer=None):
@@ -389,23 +565,28 @@ def add_cigars(result, reads, genome, workspace_mb=4096, device_id=0, tracer=Non
 
 
 def sam_lines(result, reads, genome):
-    """@HD, @SQ per contig, then one line per mapped read that carries a `cigar` (add_cigars): FLAG 0 or 16, POS 1-based, MAPQ 255
-    (not available), the CIGAR over =XID, SEQ in genome orientation, QUAL *, and NM:i:E."""
+    """@HD, @SQ per contig, then one line per mapped read that carries a `cigar` (add_cigars): FLAG 0 or 16, POS 1-based, MAPQ the
+    record's mapq (255, not available, without one: map_reads at candidates=1), the CIGAR over =XID, SEQ in genome orientation,
+    QUAL *, NM:i:E and, when a second candidate was aligned, e2:i: with its edit distance."""
     lines = ["@HD\tVN:1.6\tSO:unknown"] + ["@SQ\tSN:%s\tLN:%d" % (name, int(n)) for name, n in zip(genome.names, genome.lengths)]
     for r in result["reads"]:
         if r["status"] != "mapped" or "cigar" not in r:
             continue
         codes = assess.encode(reads[r["name"]])
         seq = decode(codes if r["strand"] == "forward" else assess.reverse_complement(codes))
-        lines.append("\t".join(str(v) for v in (r["name"], 0 if r["strand"] == "forward" else 16, r["contig"], r["start"] + 1, 255, r["cigar"],
-                                                 "*", 0, 0, seq or "*", "*", "NM:i:%d" % r["edit"])))
+        lines.append("\t".join(str(v) for v in (r["name"], 0 if r["strand"] == "forward" else 16, r["contig"], r["start"] + 1, r.get("mapq", 255),
+                                                 r["cigar"], "*", 0, 0, seq or "*", "*", "NM:i:%d" % r["edit"]) + _second_tag(r)))
     return lines
+
+
+def _second_tag(r):
+    return ("e2:i:%d" % r["edit_second"],) if r.get("edit_second") is not None else ()
 
 
 def paf_lines(result, genome):
     """The twelve PAF columns of every mapped read: the whole read is aligned (query 0 .. n), the residue-match column is M, the
-    block length M + X + I + D, the mapping quality 255 (not available).  A record that carries a `cigar` (add_cigars) gets a
-    cg:Z: tag after them."""
+    block length M + X + I + D, the mapping quality the record's mapq (255, not available, without one).  After them e2:i: when a
+    second candidate was aligned, and a cg:Z: tag for a record that carries a `cigar` (add_cigars)."""
     tlen = dict(zip(genome.names, (int(v) for v in genome.lengths)))
     lines = []
     for r in result["reads"]:
@@ -413,7 +594,7 @@ def paf_lines(result, genome):
             continue
         block = r["match"] + r["mismatch"] + r["insertion"] + r["deletion"]
         cols = (r["name"], r["read_len"], 0, r["read_len"], "+" if r["strand"] == "forward" else "-", r["contig"], tlen[r["contig"]],
-                r["start"], r["end"], r["match"], block, 255) + (("cg:Z:" + r["cigar"],) if "cigar" in r else ())
+                r["start"], r["end"], r["match"], block, r.get("mapq", 255)) + _second_tag(r) + (("cg:Z:" + r["cigar"],) if "cigar" in r else ())
         lines.append("\t".join(str(v) for v in cols))
     return lines
 
@@ -436,6 +617,8 @@ def write_outputs(out_dir, result, genome, meta=None, reads=None):
         with open(os.path.join(out_dir, "mapped.sam"), "w") as f:
             f.write("".join(ln + "\n" for ln in sam_lines(result, reads, genome)))
     report = dict(meta or {})
+    if "ambiguity" in result:
+        report.update(result["ambiguity"])
     report.update({"totals": result["totals"], "unmapped": result["unmapped"], "reads": result["reads"]})
     with open(os.path.join(out_dir, "map_report.json"), "w") as f:
         json.dump(report, f, indent=1)
@@ -443,14 +626,18 @@ def write_outputs(out_dir, result, genome, meta=None, reads=None):
 
 
 def map_command(input_path, genome_path, out_dir, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0,
-                cigar=False, seed=DEFAULT_SEED):
+                cigar=False, seed=DEFAULT_SEED, candidates=1, second_ratio=0.5):
     """The `map` command: called reads + genome -> the three outputs (with cigar: traced, and mapped.sam too); returns the report.
-    seed: "gpu" votes with vote_reads, "host" with the per-read numpy `vote`; the outputs are the same."""
+    seed: "gpu" votes with vote_reads, "host" with the per-read numpy `vote`; the outputs are the same.  candidates > 1: up to that
+    many seeds a read are aligned and the files carry a mapping quality (map_reads); the report says so."""
     seeder = seeder_of(seed, workspace_mb, device_id)
     genome = load_genome(genome_path)
     reads = assess.load_reads(input_path)
-    result = map_reads(reads, genome, min_votes, max_occ, band, workspace_mb, device_id, seeder=seeder)
+    result = map_reads(reads, genome, min_votes, max_occ, band, workspace_mb, device_id, seeder=seeder, candidates=candidates,
+                       second_ratio=second_ratio, top_seeder=top_seeder_of(seed, workspace_mb, device_id))
     meta = {"input": input_path, "genome": genome_path, "k": K, "min_votes": min_votes, "max_occ": max_occ, "band": band, "seed": seed}
+    if candidates > 1:
+        meta.update({"candidates": candidates, "second_ratio": second_ratio})
     if not cigar:
         return write_outputs(out_dir, result, genome, meta)
     add_cigars(result, reads, genome, workspace_mb, device_id)
@@ -458,14 +645,15 @@ def map_command(input_path, genome_path, out_dir, min_votes=MIN_VOTES, max_occ=M
 
 
 def assess_genome(input_path, genome_path, min_votes=MIN_VOTES, max_occ=MAX_OCC, band=BAND0, workspace_mb=4096, device_id=0,
-                  profile=False, seed=DEFAULT_SEED):
+                  profile=False, seed=DEFAULT_SEED, candidates=1, second_ratio=0.5):
     """`assess -g`: map, then assess every mapped read against its cut-out (which is in the read's orientation, so the global
     alignment runs forward); the report's strand, contig, start and end come from the mapping.  Reads that did not map are the
     report's unpaired reads.  profile: the per-read cigar and the pooled error profile as well, in the read's orientation (not the
     genome's, unlike `map --cigar`); the report's profile_orientation says so.  seed: as for map_command."""
     seeder = seeder_of(seed, workspace_mb, device_id)
     reads = assess.load_reads(input_path)
-    mapped = map_reads(reads, load_genome(genome_path), min_votes, max_occ, band, workspace_mb, device_id, seeder=seeder)
+    mapped = map_reads(reads, load_genome(genome_path), min_votes, max_occ, band, workspace_mb, device_id, seeder=seeder,
+                       candidates=candidates, second_ratio=second_ratio, top_seeder=top_seeder_of(seed, workspace_mb, device_id))
     paired, unpaired = assess.pair_reads(reads, mapped["references"])
     rows = assess.align_pairs([p[1] for p in paired], [p[2] for p in paired], device_id)
     by = {r["name"]: r for r in mapped["reads"]}

@@ -70,19 +70,27 @@ def ops_from_cigar(text, name="?"):
     return cigar_columns(text, name)[0]
 
 
-def _source(alignments, names, skipped=None, soft_clipped=0):
+def _source(alignments, names, skipped=None, soft_clipped=0, low_mapq=0):
     skip = {reason: 0 for reason in SKIP_REASONS}
     skip.update(skipped or {})
-    return {"alignments": alignments, "names": names, "used": len(alignments), "skipped": skip, "soft_clipped": int(soft_clipped)}
+    return {"alignments": alignments, "names": names, "used": len(alignments), "skipped": skip, "soft_clipped": int(soft_clipped),
+            "low_mapq": int(low_mapq)}
 
 
-def read_sam(path, genome):
+def below_mapq(mapq, min_mapq):
+    """Whether a SAM line's MAPQ fails the floor: 255 means not available and always passes."""
+    return mapq != 255 and mapq < min_mapq
+
+
+def read_sam(path, genome, min_mapq=0):
     """The alignments of a SAM file against a map.Genome, from RNAME, the 1-based POS, CIGAR and SEQ.  Lines with FLAG 0x4
     (unmapped), 0x100 (secondary) or 0x800 (supplementary), CIGAR '*' or SEQ '*' are skipped and counted per reason.  An unknown
-    contig, or an alignment that runs past its contig's end, is a ValueError.
-    -> dict(alignments=[(pos, read codes, ops)], names, used, skipped={reason: lines}, soft_clipped=read bases under 'S')."""
+    contig, or an alignment that runs past its contig's end, is a ValueError.  Of the other lines, those with a MAPQ below
+    min_mapq are dropped and counted as low_mapq (255, not available, always passes; with min_mapq 0 nothing is dropped).
+    -> dict(alignments=[(pos, read codes, ops)], names, used, skipped={reason: lines}, soft_clipped=read bases under 'S',
+    low_mapq)."""
     contig = {name: c for c, name in enumerate(genome.names)}
-    alns, names, soft = [], [], 0
+    alns, names, soft, low = [], [], 0, 0
     skipped = {reason: 0 for reason in SKIP_REASONS}
     with open(path) as f:
         for number, line in enumerate(f, 1):
@@ -96,6 +104,9 @@ def read_sam(path, genome):
                       "no_cigar" if cig == "*" else "no_seq" if seq == "*" else None)
             if reason:
                 skipped[reason] += 1
+                continue
+            if below_mapq(int(col[4]), min_mapq):
+                low += 1
                 continue
             if rname not in contig:
                 raise ValueError("%s: read %s lies on contig %s, which the genome does not have" % (path, name, rname))
@@ -112,7 +123,7 @@ def read_sam(path, genome):
             alns.append((int(genome.starts[c]) + pos - 1, codes[lead:len(codes) - trail], ops))
             names.append(name)
             soft += lead + trail
-    return _source(alns, names, skipped, soft)
+    return _source(alns, names, skipped, soft, low)
 
 
 def from_map(result, reads, genome):
@@ -335,8 +346,9 @@ def write_outputs(out_dir, result, genome, source, meta=None):
     return report
 
 
-def pileup_command(input_path, genome_path, out_dir, min_depth=3, workspace_mb=4096, device_id=0):
-    """The `pileup` command: a `map --cigar` output directory (its mapped.sam) or a SAM file + the genome -> the three outputs."""
+def pileup_command(input_path, genome_path, out_dir, min_depth=3, workspace_mb=4096, device_id=0, min_mapq=0):
+    """The `pileup` command: a `map --cigar` output directory (its mapped.sam) or a SAM file + the genome -> the three outputs.
+    min_mapq > 0: alignments below it are dropped (read_sam) and the report gains min_mapq and low_mapq, their count."""
     from . import map as map_mod
     sam = input_path
     if os.path.isdir(input_path):
@@ -344,8 +356,9 @@ def pileup_command(input_path, genome_path, out_dir, min_depth=3, workspace_mb=4
         if not os.path.exists(sam):
             raise ValueError("%s has no mapped.sam: run `chiron map` with --cigar, which writes it" % input_path)
     genome = map_mod.load_genome(genome_path)
-    source = read_sam(sam, genome)
+    source = read_sam(sam, genome, min_mapq)
     result = count(source["alignments"], genome, min_depth, workspace_mb, device_id, want_counts=True)
-    return write_outputs(out_dir, result, genome, source,
-                         {"input": input_path, "sam": sam, "genome": genome_path, "min_depth": min_depth, "workspace_mb": workspace_mb,
-                          "ins_slots": INS_SLOTS})
+    meta = {"input": input_path, "sam": sam, "genome": genome_path, "min_depth": min_depth, "workspace_mb": workspace_mb, "ins_slots": INS_SLOTS}
+    if min_mapq > 0:
+        meta.update({"min_mapq": min_mapq, "low_mapq": source["low_mapq"]})
+    return write_outputs(out_dir, result, genome, source, meta)

@@ -364,9 +364,9 @@ def variant_rows(records, genome):
     return rows
 
 
-def read_strands(path):
+def read_strands(path, min_mapq=0):
     """Per SAM line that pileup.read_sam uses, in its order: (name, FLAG 16 set, whole SEQ as codes, leading soft clip).  The same
-    lines are skipped as there (unmapped, secondary, supplementary, CIGAR '*', SEQ '*')."""
+    lines are skipped as there (unmapped, secondary, supplementary, CIGAR '*', SEQ '*', a MAPQ below min_mapq)."""
     out = []
     with open(path) as f:
         for line in f:
@@ -374,17 +374,17 @@ def read_strands(path):
                 continue
             col = line.rstrip("\r\n").split("\t")
             flag = int(col[1])
-            if flag & 0x904 or col[5] == "*" or col[9] == "*":
+            if flag & 0x904 or col[5] == "*" or col[9] == "*" or pileup.below_mapq(int(col[4]), min_mapq):
                 continue
             out.append((col[0], bool(flag & 16), assess.encode(col[9]), pileup.cigar_columns(col[5], col[0])[1]))
     return out
 
 
-def reads_from_sam(sam, genome):
+def reads_from_sam(sam, genome, min_mapq=0):
     """(pileup source, reads without logits): the alignments of pileup.read_sam and, per alignment, the read dict of this module
-    with `called` turned into signal orientation."""
-    source = pileup.read_sam(sam, genome)
-    strands = read_strands(sam)
+    with `called` turned into signal orientation.  min_mapq: as for pileup.read_sam; the source's low_mapq counts the drops."""
+    source = pileup.read_sam(sam, genome, min_mapq)
+    strands = read_strands(sam, min_mapq)
     if [s[0] for s in strands] != source["names"]:
         raise ValueError("%s: the strands and the alignments name different reads" % sam)
     reads = []
@@ -422,7 +422,8 @@ def polish_command(args):
         if not os.path.exists(sam):
             raise ValueError("%s has no mapped.sam: run `chiron map` with --cigar, which writes it" % args.input)
     genome = map_mod.load_genome(args.genome)
-    source, reads = reads_from_sam(sam, genome)
+    min_mapq = getattr(args, "min_mapq", 0)
+    source, reads = reads_from_sam(sam, genome, min_mapq)
     signals = dict(label.find_signals(args.signal))
     spec, weights, _ = model_mod.load_model(args.model, allow_synthetic=args.synthetic_weights)
     with Engine(spec, weights, max_batch=args.batch_size, segment_len=args.segment_len, device_id=args.device, dtype=args.dtype) as eng:
@@ -438,4 +439,6 @@ def polish_command(args):
             "dtype": args.dtype, "min_depth": args.min_depth, "workspace_mb": args.workspace_mb, "alignments_used": source["used"],
             "alignments_skipped": source["skipped"],
             "vote_variants": len(pileup.variants(piled["call"], piled["depth"], piled["counts"], genome))}
+    if min_mapq > 0:
+        meta.update({"min_mapq": min_mapq, "low_mapq": source["low_mapq"]})
     return write_outputs(args.output, result, genome, meta)

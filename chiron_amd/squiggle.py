@@ -429,11 +429,14 @@ def _sam_of(path):
     return path
 
 
-def load_sample(sam, signal_dir, genome, engine, batch_size):
+def load_sample(sam, signal_dir, genome, engine, batch_size, min_mapq=0, dropped=None):
     """The reads of one sample as `prepare` takes them: polish.reads_from_sam, and for every read with a .signal file its samples
-    (`raw`, as `call` reads them), its frame logits and the windows' frame counts (label.read_frames)."""
+    (`raw`, as `call` reads them), its frame logits and the windows' frame counts (label.read_frames).  min_mapq: as for
+    pileup.read_sam; the number of records it drops is appended to `dropped`."""
     from . import signal_io
-    _, reads = polish.reads_from_sam(sam, genome)
+    source, reads = polish.reads_from_sam(sam, genome, min_mapq)
+    if dropped is not None:
+        dropped.append(source["low_mapq"])
     signals = dict(label.find_signals(signal_dir))
     for r in reads:
         if r["name"] in signals:
@@ -458,8 +461,9 @@ def squiggle_command(args):
     spec, weights, _ = model_mod.load_model(args.model, allow_synthetic=args.synthetic_weights)
     with Engine(spec, weights, max_batch=args.batch_size, segment_len=args.segment_len, device_id=args.device, dtype=args.dtype) as eng:
         ratio = eng.ratio
-        loaded = load_sample(sam, args.signal, genome, eng, args.batch_size)
-        control = load_sample(control_sam, args.control_signal, genome, eng, args.batch_size) if control_sam else None
+        min_mapq, low = getattr(args, "min_mapq", 0), []
+        loaded = load_sample(sam, args.signal, genome, eng, args.batch_size, min_mapq, low)
+        control = load_sample(control_sam, args.control_signal, genome, eng, args.batch_size, min_mapq, low) if control_sam else None
     kw = dict(segment_len=args.segment_len, ratio=ratio, mode=args.normalize, band=args.band, max_band=args.max_band,
               workspace_mb=args.workspace_mb, device_id=args.device)
     a = sample(loaded, genome, kmer=args.kmer or 0, **kw)
@@ -471,13 +475,15 @@ def squiggle_command(args):
               "dtype": args.dtype, "normalize": args.normalize, "scale": SCALE, "min_events": args.min_events, "kmer": args.kmer or 0,
               "band": args.band, "max_band": args.max_band, "workspace_mb": args.workspace_mb, "ratio": ratio}
     report.update(a["report"])
+    if min_mapq > 0:
+        report.update({"min_mapq": min_mapq, "low_mapq": low[0]})
     if control is not None:
         b = sample(control, genome, **kw)
         result = compare(a["planes"].transpose(1, 0, 2), b["planes"].transpose(1, 0, 2), args.min_events)
         with open(os.path.join(args.output, "compare.tsv"), "w") as f:
             f.write("".join(compare_lines(result, genome)))
         files.append("compare.tsv")
-        report["control"] = dict(b["report"], sam=control_sam, signal=args.control_signal)
+        report["control"] = dict(b["report"], sam=control_sam, signal=args.control_signal, **({"low_mapq": low[1]} if min_mapq > 0 else {}))
         report["compared"] = int(result["keep"].sum())
     if args.kmer:
         with open(os.path.join(args.output, "kmer_levels.tsv"), "w") as f:

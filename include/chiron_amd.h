@@ -414,7 +414,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *
  * Caller's memory.  This holds for every call below that takes a workspace, a tape or a device output buffer from its caller --
  * chiron_ctc_loss, chiron_rnn_train_forward / _backward, chiron_cnn_train_forward / _backward, chiron_align_pairs,
- * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
+ * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_seed_candidates, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
  * chiron_pileup and chiron_signal_levels; their own comments say "uninitialised" or name the size function and mean this:
  *   - workspace, tape and output buffers may hold anything on entry: the results do not depend on it (the library clears what it
  *     needs cleared, on the call's stream);
@@ -708,6 +708,26 @@ chiron_status chiron_seed_workspace_size(int64_t n_index, int64_t genome_len, in
 chiron_status chiron_seed_reads(int32_t device_id, const uint32_t* idx_val, const int32_t* idx_pos, int64_t n_index, int64_t genome_len,
                                 const uint8_t* codes, const int64_t* read_off, int64_t reads, uint32_t flags, int32_t* votes_out,
                                 int32_t* second_out, int32_t* strand_out, int64_t* delta_out, int64_t* g_out, void* workspace, void* stream);
+
+/* Up to max_cand candidates a read instead of one, equal to map.vote_top (chiron_amd/map.py).  Bins, scores and strands are those
+ * of chiron_seed_reads.  The picks are made greedily: among the (strand, bin) pairs that hold a hit and are not suppressed, the
+ * largest score, ties to strand 0, then to the smaller bin; the picking stops when nothing is left, when that score is below
+ * min_score, or after max_cand picks.  A pick at bin beta suppresses the bins b of its own strand with |b - beta| <= n / 256 + 2
+ * (the complement of second_out's "far" rule, so pick 0 is chiron_seed_reads' candidate and pick 1's votes are its second_out).
+ * Each pick's (delta, g) is the hit of rank (votes - 1) / 2 among the hits of bins beta and beta + 1 ordered by (delta, g).
+ *
+ * count_out: HOST int32 [reads], the number of picks; votes_out, strand_out: HOST int32 and delta_out, g_out: HOST int64, each
+ * [reads][max_cand], pick c of read q at q * max_cand + c, zeros from count_out[q] on.  Everything else is as for
+ * chiron_seed_reads, refusals included, with CHIRON_ERR_INVALID also for max_cand outside 1 .. CHIRON_SEED_MAX_CANDIDATES or
+ * min_score < 1.  One launch: the k-mers are looked up and counted once a read, each pick replays the hits (csrc/seed.hip).
+ * Workspace: that of chiron_seed_workspace_size with 4 + 16 max_cand bytes of results a read in place of 20.                    */
+#define CHIRON_SEED_MAX_CANDIDATES 8
+chiron_status chiron_seed_candidates_workspace_size(int64_t n_index, int64_t genome_len, int64_t reads, int64_t max_read, int64_t total_bases,
+                                                    int32_t max_cand, size_t* bytes);
+chiron_status chiron_seed_candidates(int32_t device_id, const uint32_t* idx_val, const int32_t* idx_pos, int64_t n_index, int64_t genome_len,
+                                     const uint8_t* codes, const int64_t* read_off, int64_t reads, int32_t max_cand, int32_t min_score,
+                                     uint32_t flags, int32_t* count_out, int32_t* votes_out, int32_t* strand_out, int64_t* delta_out,
+                                     int64_t* g_out, void* workspace, void* stream);
 
 /* CTC forced alignment: given a read's frame scores and the bases it is known to have, the best monotone assignment of frames
  * to bases (what a resquiggler gives the reference project; here from the model's own logits).  Read r has frames
