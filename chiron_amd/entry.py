@@ -335,7 +335,7 @@ def squiggle(args):
     """The reads' current levels on the genome: squiggle.squiggle_command (the samples of every called base reduced to a level and the
     levels summed per position and strand on the GPU).  Writes <out>/levels.tsv and <out>/squiggle_report.json, with --control
     <out>/compare.tsv (Welch's t per position against the control sample), with --kmer <out>/kmer_levels.tsv and with --events
-    <out>/events/<read>.tsv; exits non-zero on an input without a mapped.sam or when no read could be used."""
+    <out>/events/<read>.tsv; with --refine the base borders are first moved to where the samples meet a level table; exits non-zero on an input without a mapped.sam or when no read could be used."""
     import logging
     from . import squiggle as squiggle_mod
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -626,6 +626,12 @@ def build_parser():
                     help="Drop alignments whose MAPQ is below this (`map --candidates` writes one; 255, not available, always passes).")
     sq.add_argument("--kmer", type=int, default=0, help="Also write kmer_levels.tsv, the level table of the genome K-mers (1 to 10).")
     sq.add_argument("--events", action="store_true", help="Also write events/<read>.tsv, one row per base.")
+    sq.add_argument("--refine", default=None, metavar="KMER_LEVELS_TSV",
+                    help="Move every base border to where the samples meet this level table (the kmer_levels.tsv of an earlier run with "
+                         "--kmer): an exact banded DTW on the GPU, 64 candidates a border, of the sample and the control alike, before "
+                         "anything else is computed.")
+    sq.add_argument("--refine-min-events", dest="refine_min_events", type=int, default=5,
+                    help="Fewest events a k-mer of the --refine table must have for its level to be used.")
     sq.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
     sq.add_argument("-b", "--batch_size", type=int, default=1100, help="Windows per engine batch.")
     sq.add_argument("--band", type=int, default=256, help="First half-width of the frame alignment's band, in CTC states; 0: the full table.")

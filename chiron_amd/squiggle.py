@@ -16,7 +16,12 @@ A read here is polish.py's dict(name, pos, ops, reverse, called, lead) plus `sig
 complementary k-mers.
 
 The reduction is the library's; everything else is plain numpy.  There is no CPU fallback: the hooks reducer= and frame_aligner= exist
-for the tests' reference."""
+for the tests' reference.
+
+With a level table (`squiggle --refine`, the kmer_levels.tsv of an earlier run) the borders are first moved to where the samples
+change level: expected_levels gives every base the level of its k-mer, refine_items cuts a read into the runs of bases that have
+one, and the library's chiron_signal_refine (csrc/refine.hip) runs an exact banded DTW of each run's samples against its levels,
+64 candidates a border around the frame alignment's.  refiner= replaces that stage in the tests."""
 import json
 import os
 
@@ -37,6 +42,9 @@ LEVEL_COLUMNS = ("contig", "pos", "strand", "ref", "events", "mean_dwell", "mean
 COMPARE_COLUMNS = ("contig", "pos", "strand", "ref", "events_a", "mean_a", "sd_a", "events_b", "mean_b", "sd_b", "t", "df", "effect")
 KMER_COLUMNS = ("kmer", "events", "mean_dwell", "mean", "sd")
 EVENT_COLUMNS = ("start", "length", "level", "contig", "pos")
+REFINE_HALF, INFEASIBLE = _lib.REFINE_HALF, _lib.REFINE_INFEASIBLE
+UNKNOWN = EMPTY                          # a base without an expected level, a k-mer without a table entry
+REFINE_COUNTS = ("items", "bases", "infeasible", "borders", "moved", "mean_move", "cost")
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
@@ -266,6 +274,185 @@ def kmer_levels(reads, genome, k, workspace_mb=4096, device_id=0, reducer=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
+# refinement of the borders against a level table
+# ----------------------------------------------------------------------------------------------------------------------------
+def load_level_table(path, min_events=5):
+    """The kmer_levels.tsv that `squiggle --kmer K` writes -> (K, int32 [4^K]): rint(mean * SCALE) for a k-mer with at least
+    min_events events, UNKNOWN for every other."""
+    with open(path) as f:
+        rows = [ln.rstrip("\n").split("\t") for ln in f if ln.strip()]
+    if not rows or tuple(rows[0]) != KMER_COLUMNS:
+        raise ValueError("%s is not a kmer_levels.tsv: its first line is not %s" % (path, " ".join(KMER_COLUMNS)))
+    if len(rows) < 2:
+        raise ValueError("%s holds no k-mer" % path)
+    k = len(rows[1][0])
+    if not 1 <= k <= MAX_K:
+        raise ValueError("%s: k-mers of %d bases, outside 1 .. %d" % (path, k, MAX_K))
+    table = np.full(4 ** k, UNKNOWN, dtype=np.int32)
+    for row in rows[1:]:
+        if len(row) != len(KMER_COLUMNS) or len(row[0]) != k or set(row[0]) - set("ACGT"):
+            raise ValueError("%s: a row of %d fields with the k-mer %r among %d-mers" % (path, len(row), row[0], k))
+        if int(row[1]) >= min_events:
+            code = 0
+            for c in row[0]:
+                code = code * 4 + "ACGT".index(c)
+            table[code] = int(np.clip(np.rint(float(row[3]) * SCALE), -32767, 32767))
+    return k, table
+
+
+def table_of(kmer_planes, min_events=5):
+    """The table load_level_table would read from kmer_lines(kmer_planes): without the file in between, and so without the
+    rounding of its five decimals."""
+    n, mean, _ = moments(kmer_planes)
+    with np.errstate(invalid="ignore"):
+        level = np.clip(np.rint(np.where(n > 0, mean, 0.0)), -32767, 32767).astype(np.int32)
+    return np.where(n >= max(int(min_events), 1), level, UNKNOWN).astype(np.int32)
+
+
+def expected_levels(read, genome, table, k):
+    """int32 [bases], signal order: the table's level of every base's k-mer, the base itself at index k // 2 of it.  For the base of
+    an '=' or 'X' column that is the genome k-mer of kmer_bins; for an inserted or clipped base it is the k-mer of the read's own
+    called bases around it, in signal order.  UNKNOWN where the k-mer leaves the genome or the read, holds a code above 3, or has no
+    entry in the table."""
+    table = np.asarray(table, dtype=np.int32)
+    if table.shape != (4 ** k,):
+        raise ValueError("a table of %s entries for k = %d" % (table.shape, k))
+    called = np.asarray(read["called"], dtype=np.int64)
+    n, h = len(called), k // 2
+    code = np.full(n, -1, dtype=np.int64)
+    if n >= k:
+        win = called[np.arange(n - k + 1)[:, None] + np.arange(k)[None, :]]
+        own = (win * (4 ** np.arange(k - 1, -1, -1, dtype=np.int64))[None, :]).sum(axis=1)
+        code[h:h + n - k + 1] = np.where((win <= 3).all(axis=1), own, -1)
+    _, idx = _columns(read)
+    code[idx] = kmer_bins(read, genome, k)[idx]
+    return np.where(code >= 0, table[np.maximum(code, 0)], UNKNOWN).astype(np.int32)
+
+
+def refine_items(levels):
+    """[(first base, one past the last)] of the maximal runs of bases whose level is not UNKNOWN."""
+    known = np.concatenate([[False], np.asarray(levels) != UNKNOWN, [False]])
+    edges = np.flatnonzero(known[1:] != known[:-1])
+    return [(int(a), int(b)) for a, b in zip(edges[0::2], edges[1::2])]
+
+
+def refine_workspace_size(items, samples, bases):
+    """chiron_signal_refine_workspace_size (host-only)."""
+    return _lib.sized("chiron_signal_refine_workspace_size", int(items), int(samples), int(bases))
+
+
+def refine_call(signals, levels, starts, device_id=0):
+    """One chiron_signal_refine call.  Per item: its int16 samples, its int32 levels [L] and its int32 starts [L + 1], relative to
+    its first sample.  -> ([int32 refined starts per item], int64 costs [items], INFEASIBLE for an item that keeps its starts)."""
+    if not len(signals) == len(levels) == len(starts):
+        raise ValueError("%d signals, %d level arrays, %d start arrays" % (len(signals), len(levels), len(starts)))
+    items = len(signals)
+    sig = [np.ascontiguousarray(s, dtype=np.int16).reshape(-1) for s in signals]
+    lv = [np.ascontiguousarray(e, dtype=np.int32).reshape(-1) for e in levels]
+    st = [np.ascontiguousarray(s, dtype=np.int32).reshape(-1) for s in starts]
+    for i in range(items):
+        if len(st[i]) != len(lv[i]) + 1:
+            raise ValueError("item %d: %d start entries for %d bases, one more is needed" % (i, len(st[i]), len(lv[i])))
+    sample_off, base_off = label._offsets([len(s) for s in sig]), label._offsets([len(e) for e in lv])
+    n_bases = int(base_off[-1])
+    samples = np.ascontiguousarray(np.concatenate(sig + [np.zeros(1, np.int16)]))
+    level = np.ascontiguousarray(np.concatenate(lv + [np.zeros(1, np.int32)]))
+    start = np.ascontiguousarray(np.concatenate(st + [np.zeros(1, np.int32)]))
+    out = np.zeros(n_bases + items + 1, dtype=np.int32)
+    cost = np.zeros(max(items, 1), dtype=np.int64)
+
+    def split():
+        return [out[base_off[i] + i:base_off[i + 1] + i + 1].copy() for i in range(items)], cost[:items].copy()
+    args = (samples.ctypes.data, sample_off.ctypes.data, level.ctypes.data, start.ctypes.data, base_off.ctypes.data, items, 0, out.ctypes.data,
+            cost.ctypes.data)
+    if n_bases == 0:                                    # nothing to move: the library touches no device
+        _lib.check(_lib.load().chiron_signal_refine(device_id, *args, None, None))
+        return split()
+    lib, ws, stream = _lib.device_workspace(lambda: refine_workspace_size(items, int(sample_off[-1]), n_bases), device_id, "squiggle.refine",
+                                            "refine kernel")
+    _lib.check(lib.chiron_signal_refine(device_id, *args, ws.data_ptr(), stream))
+    del ws
+    return split()
+
+
+def plan_refine_batches(counts, budget_bytes):
+    """counts: (items, samples, bases) per read.  Consecutive runs of reads [(first, last + 1)] whose call fits the budget, each the
+    longest that does (the size grows with every read: bisection); a read that alone exceeds it gets a run of its own."""
+    c = np.concatenate([np.zeros((1, 3), np.int64), np.cumsum(np.asarray(counts, dtype=np.int64).reshape(-1, 3), axis=0)])
+    n, runs, first = len(c) - 1, [], 0
+    while first < n:
+        lo, hi = first + 1, n
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if refine_workspace_size(*(c[mid] - c[first]).tolist()) <= budget_bytes:
+                lo = mid
+            else:
+                hi = mid - 1
+        runs.append((first, lo))
+        first = lo
+    return runs
+
+
+def refine(reads, genome, table, k, workspace_mb=4096, device_id=0, refiner=None):
+    """Moves the borders of every read to where its samples meet the table's levels and replaces its `starts`.  Per read the items
+    are the runs of refine_items(expected_levels(...)); a border outside them, and an item the DP finds infeasible, stays.  The
+    calls are planned against workspace_mb with the host-only size function.  refiner(signals, levels, starts) -> (starts, costs)
+    replaces the library call (the tests' reference).
+    -> dict(items, bases in them, infeasible items, borders inside items, moved of them, mean_move = mean |move| in samples over
+    those borders, cost of the feasible items, calls)."""
+    if refiner is None:
+        import torch  # noqa: F401  before the planner loads the library: torch's ROCm runtime has to come up first (_lib.py)
+
+        def refiner(signals, levels, starts):
+            return refine_call(signals, levels, starts, device_id)
+    reads = list(reads)
+    per_read = []
+    for r in reads:
+        lv = expected_levels(r, genome, table, k)
+        st = np.asarray(r["starts"], dtype=np.int32)
+        runs = refine_items(lv)
+        per_read.append((lv, runs, (len(runs), sum(int(st[b] - st[a]) for a, b in runs), sum(b - a for a, b in runs))))
+    out = dict.fromkeys(REFINE_COUNTS, 0)
+    moved_by = 0
+    batches = plan_refine_batches([c for _, _, c in per_read], int(workspace_mb * (1 << 20))) if reads else []
+    for first, last in batches:
+        signals, levels_, starts, where = [], [], [], []
+        for i in range(first, last):
+            lv, runs, _ = per_read[i]
+            st = np.asarray(reads[i]["starts"], dtype=np.int32)
+            for a, b in runs:
+                signals.append(reads[i]["signal"][st[a]:st[b]])
+                levels_.append(lv[a:b])
+                starts.append(st[a:b + 1] - st[a])
+                where.append((i, a, b))
+        if not where:
+            continue
+        got, cost = refiner(signals, levels_, starts)
+        new = {}
+        for (i, a, b), s_in, s, c in zip(where, starts, got, cost):
+            out["items"] += 1
+            out["bases"] += b - a
+            if int(c) == INFEASIBLE:
+                out["infeasible"] += 1
+                continue
+            st = new.setdefault(i, np.array(reads[i]["starts"], dtype=np.int32))
+            st[a:b + 1] = st[a] + np.asarray(s, dtype=np.int32)
+            move = np.abs(np.asarray(s, dtype=np.int64) - s_in)[1:-1]
+            out["borders"] += len(move)
+            out["moved"] += int((move > 0).sum())
+            moved_by += int(move.sum())
+            out["cost"] += int(c)
+        for i, st in new.items():
+            reads[i]["starts"] = st
+    out["mean_move"] = moved_by / out["borders"] if out["borders"] else 0.0
+    out["calls"] = len(batches)
+    return out
+
+
+_refine_reads = refine                   # sample() has an argument of that name
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
 # statistics
 # ----------------------------------------------------------------------------------------------------------------------------
 def moments(planes):
@@ -339,14 +526,18 @@ def prepare(reads, segment_len, ratio, mode="mad", band=label.BAND0, max_band=la
 
 
 def sample(reads, genome, segment_len, ratio, mode="mad", band=label.BAND0, max_band=label.MAX_BAND, workspace_mb=4096, device_id=0,
-           frame_aligner=None, reducer=None, kmer=0):
-    """One sample from loaded reads to planes: prepare, levels and, with kmer > 0, kmer_levels.
-    -> dict(reads kept, planes, levels, tiles, kmer_planes or None, report)."""
+           frame_aligner=None, reducer=None, kmer=0, refine=None, refiner=None):
+    """One sample from loaded reads to planes: prepare, with refine = (table, k) the refinement of the borders (`refine` above;
+    refiner= is its hook), levels and, with kmer > 0, kmer_levels.
+    -> dict(reads kept, planes, levels, tiles, kmer_planes or None, report); the report has a `refine` section when refined."""
     kept, drops = prepare(reads, segment_len, ratio, mode, band, max_band, workspace_mb, device_id, frame_aligner)
+    refined = _refine_reads(kept, genome, refine[0], refine[1], workspace_mb, device_id, refiner) if refine is not None else None
     got = levels(kept, genome, workspace_mb, device_id, reducer)
     report = {"reads": {"total": len(reads), "used": len(kept), "dropped": drops}, "tiles": got["tiles"],
               "bases": int(sum(len(r["called"]) for r in kept)), "samples": int(sum(len(r["signal"]) for r in kept)),
               "events": int(got["planes"][:, EVENTS].sum())}
+    if refined is not None:
+        report["refine"] = refined
     return {"reads": kept, "planes": got["planes"], "levels": got["levels"], "tiles": got["tiles"], "report": report,
             "kmer_planes": kmer_levels(kept, genome, kmer, workspace_mb, device_id, reducer) if kmer else None}
 
@@ -455,6 +646,10 @@ def squiggle_command(args):
         raise ValueError("--kmer %d outside 1 .. %d" % (args.kmer, MAX_K))
     if bool(args.control) != bool(args.control_signal):
         raise ValueError("--control and --control-signal go together")
+    refine_path = getattr(args, "refine", None)
+    table = None
+    if refine_path:
+        table = load_level_table(refine_path, getattr(args, "refine_min_events", 5))[::-1]            # (table, k): read before the engine starts
     sam = _sam_of(args.input)
     control_sam = _sam_of(args.control) if args.control else None
     genome = map_mod.load_genome(args.genome)
@@ -465,7 +660,7 @@ def squiggle_command(args):
         loaded = load_sample(sam, args.signal, genome, eng, args.batch_size, min_mapq, low)
         control = load_sample(control_sam, args.control_signal, genome, eng, args.batch_size, min_mapq, low) if control_sam else None
     kw = dict(segment_len=args.segment_len, ratio=ratio, mode=args.normalize, band=args.band, max_band=args.max_band,
-              workspace_mb=args.workspace_mb, device_id=args.device)
+              workspace_mb=args.workspace_mb, device_id=args.device, refine=table)
     a = sample(loaded, genome, kmer=args.kmer or 0, **kw)
     os.makedirs(args.output, exist_ok=True)
     files = ["levels.tsv"]
@@ -475,6 +670,9 @@ def squiggle_command(args):
               "dtype": args.dtype, "normalize": args.normalize, "scale": SCALE, "min_events": args.min_events, "kmer": args.kmer or 0,
               "band": args.band, "max_band": args.max_band, "workspace_mb": args.workspace_mb, "ratio": ratio}
     report.update(a["report"])
+    if table is not None:                                     # sample() put the counts there; the table's own facts join them
+        report["refine"] = dict(report["refine"], table=refine_path, k=table[1], min_events=getattr(args, "refine_min_events", 5),
+                                kmers_known=int((table[0] != UNKNOWN).sum()))
     if min_mapq > 0:
         report.update({"min_mapq": min_mapq, "low_mapq": low[0]})
     if control is not None:

@@ -415,7 +415,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  * Caller's memory.  This holds for every call below that takes a workspace, a tape or a device output buffer from its caller --
  * chiron_ctc_loss, chiron_rnn_train_forward / _backward, chiron_cnn_train_forward / _backward, chiron_align_pairs,
  * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_seed_candidates, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
- * chiron_pileup and chiron_signal_levels; their own comments say "uninitialised" or name the size function and mean this:
+ * chiron_pileup, chiron_signal_levels and chiron_signal_refine; their own comments say "uninitialised" or name the size function and mean this:
  *   - workspace, tape and output buffers may hold anything on entry: the results do not depend on it (the library clears what it
  *     needs cleared, on the call's stream);
  *   - every element of every output is written, the rows and frames that carry no result included (frames past seq_len, skipped and
@@ -423,7 +423,8 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *     chiron_cnn_train_forward (only the statistics' slots are written) and a failed pair's slice of chiron_align_trace's ops_out;
  *   - nothing outside the bytes that the call's *_workspace_size / *_train_sizes function names, and outside the outputs' own
  *     extents, is read or written: a caller may pack other data right behind a workspace of exactly that size.
- * tests/test_gpu_workspace.py holds every one of these calls to the three parts (chiron_signal_levels: tests/test_gpu_squiggle.py). */
+ * tests/test_gpu_workspace.py holds every one of these calls to the three parts (chiron_signal_levels: tests/test_gpu_squiggle.py; chiron_signal_refine:
+ * tests/test_gpu_refine.py). */
 #define CHIRON_CTC_WANT_GRAD 1u
 #define CHIRON_CTC_TRUSTED 2u   /* chiron_ctc_loss: the caller has checked seq_len / labels / label_len: no read-back, no sync */
 #define CHIRON_CTC_MAX_T 8192
@@ -992,6 +993,61 @@ chiron_status chiron_signal_workspace_size(int64_t reads, int64_t samples, int64
 chiron_status chiron_signal_levels(int32_t device_id, const int16_t* samples, const int64_t* sample_off, const int32_t* start,
                                    const int64_t* base_off, const int32_t* bin, int64_t reads, int64_t bins, uint32_t flags,
                                    int64_t* planes_out, int32_t* level_out, void* workspace, void* stream);
+
+/* Signal refinement (resquiggle): move the borders between a read's bases to where the samples change level, by an exact banded
+ * dynamic-time-warping DP of the samples against the level each base is expected to have (a k-mer level table's, for `squiggle
+ * --refine`), seeded by borders that are roughly right (the CTC frame alignment's).
+ *
+ * An item is a stretch of consecutive bases of one read that all have an expected level.  Item i has S_i = sample_off[i+1] -
+ * sample_off[i] int16 samples x, samples[sample_off[i] ..), L_i = base_off[i+1] - base_off[i] bases with levels e[0 .. L_i) =
+ * level[base_off[i] ..), int32 inside -32767 .. 32767, and L_i + 1 initial starts a[0 .. L_i] = start_in[base_off[i] + i ..),
+ * laid out as chiron_signal_levels lays out `start`: relative to the item's first sample, never decreasing, inside 0 .. S_i.
+ *
+ * The refined starts s[0 .. L] are the integers with
+ *   s[0] = a[0] and s[L] = a[L],
+ *   s strictly increasing (every base gets at least one sample),
+ *   a[n] - CHIRON_REFINE_HALF <= s[n] <= a[n] + CHIRON_REFINE_HALF - 1 for 0 < n < L (64 candidates a border),
+ * that minimise
+ *   cost = sum over n of sum over t in s[n] .. s[n+1]) of |x[t] - e[n]|,
+ * an exact integer below 2^47.  Among the minimal solutions the one with the smallest s[L-1] is taken, among those the one with
+ * the smallest s[L-2], and so on down to s[1].  As a recurrence over the borders, with P the prefix sum of |x - e[n-1]|:
+ *   F[0][a[0]] = 0,   F[n][s] = P(s) + min over candidates s' < s of border n-1 of (F[n-1][s'] - P(s')),   cost = F[L][a[L]],
+ * and the predecessor of (n, s) is the SMALLEST s' that attains the minimum.  Where no such s exists (a[L] - a[0] < L, or bases
+ * crowd more than their windows allow) cost_out is CHIRON_REFINE_INFEASIBLE and the item's start_out is a copy of its start_in.
+ * An item without a base (L = 0) has cost 0 and keeps its one entry.  The samples before a[0] and from a[L] on are never read.
+ * Everything is an integer, so the result is a property of the inputs.  A window wider than 64 is not offered: a second call from
+ * the refined starts moves a border further.
+ *
+ * refine_kernel (csrc/refine.hip): a wave an item, the items dealt to the launch's waves in a loop, CHIRON_REFINE_THREADS / 64
+ * waves a workgroup and at most CHIRON_REFINE_MAX_GROUPS workgroups, no workgroup barrier.  The borders are rows that run in
+ * sequence; the 64 lanes are a border's candidates.  A row loads the 64 + (a[n] - a[n-1]) samples both windows span in pieces of
+ * 64, scans |x - e| in int32 with an int64 carry (a piece sums below 2^23), takes a wave prefix-min of F - P in int64 and shuffles
+ * it by the window shift.  The lanes that hold a strict new prefix minimum are one ballot, 8 bytes a base in the workspace; the
+ * predecessor of a candidate is the highest set bit below it, and the same wave walks the rows back after its forward pass, 64
+ * rows of masks per load.  Every offset is 64-bit.
+ *
+ * Workspace (device memory), each part rounded up to 256 bytes: the two offset arrays (8 bytes an item + 8 each), 2 bytes a
+ * sample, 4 bytes a base of levels, twice 4 bytes a base and item of starts (in and out), 8 bytes a base of masks, 8 bytes an item
+ * of costs.  Larger values of any argument are fine.  Host-only.  CHIRON_ERR_INVALID: a negative argument.  CHIRON_ERR_OVERFLOW:
+ * items > 2^31 - 1, samples > CHIRON_SIGNAL_MAX_SAMPLES, bases > 2^31 - 1.                                                       */
+#define CHIRON_REFINE_HALF 32             /* candidates of a border: a[n] - 32 .. a[n] + 31, a wave lane each */
+#define CHIRON_REFINE_INFEASIBLE INT64_MAX
+#define CHIRON_REFINE_THREADS 256
+#define CHIRON_REFINE_MAX_GROUPS 2048
+chiron_status chiron_signal_refine_workspace_size(int64_t items, int64_t samples, int64_t bases, size_t* bytes);
+
+/* Refines `items` items in one launch.  samples, sample_off (int64 [items + 1]), level, start_in and base_off (int64 [items + 1])
+ * are HOST memory, the offsets non-negative and non-decreasing.  Outputs, HOST memory: start_out int32 [base_off[items] -
+ * base_off[0] + items], item i's L_i + 1 entries at base_off[i] - base_off[0] + i; cost_out int64 [items].  workspace: device
+ * memory on device_id of chiron_signal_refine_workspace_size(items, the call's samples, the call's bases) bytes ("Caller's memory"
+ * above).  flags: 0 (reserved).  Copies the inputs in, runs refine_kernel on `stream` (a hipStream_t; NULL = the null stream) and
+ * synchronises it before returning.  CHIRON_ERR_INVALID: unknown flags, a negative count, a null array that is needed, a negative
+ * or decreasing offset, a start entry that decreases or leaves 0 .. S_i, a level outside -32767 .. 32767.  CHIRON_ERR_OVERFLOW: as
+ * the size function.  All of it before anything is copied or launched.  items == 0 touches no device and writes nothing; items
+ * without any base touch no device either: start_out is start_in and every cost is 0.                                          */
+chiron_status chiron_signal_refine(int32_t device_id, const int16_t* samples, const int64_t* sample_off, const int32_t* level,
+                                   const int32_t* start_in, const int64_t* base_off, int64_t items, uint32_t flags, int32_t* start_out,
+                                   int64_t* cost_out, void* workspace, void* stream);
 
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
