@@ -35,6 +35,8 @@ SCORE_MAX_FRAMES, SCORE_MAX_LABEL, SCORE_THREADS, SCORE_MAX_GROUPS = 4096, 127, 
 DEMUX_MAX_PATTERN, DEMUX_MAX_WINDOW, DEMUX_MAX_PATTERNS, DEMUX_THREADS, DEMUX_MAX_GROUPS, DEMUX_NONE = 64, 4096, 65536, 256, 2048, 0x7FFFFFFF
 SIGNAL_PLANES, SIGNAL_EMPTY, SIGNAL_MAX_SAMPLES, SIGNAL_MAX_BINS, SIGNAL_THREADS, SIGNAL_MAX_GROUPS = 4, -(1 << 31), 0x7FFFFFFF, 1 << 28, 256, 2048
 REFINE_HALF, REFINE_INFEASIBLE, REFINE_THREADS, REFINE_MAX_GROUPS = 32, (1 << 63) - 1, 256, 2048
+LOCATE_BREAK, LOCATE_NONE, LOCATE_MAX_QUERY, LOCATE_BLOCK, LOCATE_MAX_REF, LOCATE_MAX_CELLS = -(1 << 31), (1 << 31) - 1, 16384, 1024, 1 << 28, 1 << 40
+LOCATE_CHUNK, LOCATE_THREADS, LOCATE_MAX_GROUPS = 64, 256, 2048
 PILEUP_INS_SLOTS, PILEUP_MAX_COLUMNS, PILEUP_MAX_TILE, PILEUP_THREADS = 4, 1 << 24, 1 << 28, 256
 PILEUP_PLANES = 6 + 5 * PILEUP_INS_SLOTS + 1
 PILEUP_CHUNK = 4 * PILEUP_THREADS    # columns a workgroup of csrc/pileup.hip loads before it scans them, 256 at a time
@@ -183,6 +185,9 @@ SYMBOLS = [
     ("chiron_signal_refine_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     ("chiron_signal_refine", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_signal_locate_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    ("chiron_signal_locate", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_uint32, C.c_void_p]),
     ("chiron_last_error", C.c_char_p, []),
     ("chiron_device_pci_bus_id", C.c_int, [C.c_int32, C.c_char_p, C.c_size_t]),
     ("chiron_abi_version", C.c_int32, []),

@@ -351,6 +351,24 @@ def squiggle(args):
     return report
 
 
+def locate(args):
+    """Where on the genome raw signal comes from, without calling it: locate.locate_command (the reads' first samples against the
+    expected levels of both strands under a k-mer level table, by subsequence DTW on the GPU).  Writes <out>/located.tsv and
+    <out>/locate_report.json; exits non-zero on a file that is no level table or when no read gave a query."""
+    from . import locate as locate_mod
+    try:
+        report = locate_mod.locate_command(args)
+    except ValueError as e:
+        sys.exit("locate: %s" % e)
+    s = report["status"]
+    print("locate: %d of %d reads used against %d columns in %d calls; %d placed, %d ambiguous, %d unplaced; wrote %s"
+          % (report["reads"]["used"], report["reads"]["total"], report["columns"], report["batches"], s["placed"], s["ambiguous"], s["unplaced"],
+             ", ".join(report["files"])))
+    if report["reads"]["used"] == 0:
+        sys.exit("locate: no read of %s gave a query (%s)" % (report["signal"], report["reads"]["dropped"]))
+    return report
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -643,6 +661,32 @@ def build_parser():
     sq.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
                     help="Use seeded synthetic weights when the model folder has no checkpoint data.")
     sq.set_defaults(func=squiggle)
+    lo = subparsers.add_parser("locate", description="Place raw signal on a genome without calling it: the first samples of every read "
+                               "against the expected levels of both strands under a k-mer level table, by exact subsequence dynamic "
+                               "time warping on the GPU",
+                               help="Where on a genome raw signal comes from, by subsequence DTW against a level table.")
+    lo.add_argument("-s", "--signal", required=True, help="Output folder of `call` (its raw/ is read), or a folder of .signal or .fast5 files.")
+    lo.add_argument("-g", "--genome", required=True, help="The genome FASTA.")
+    lo.add_argument("--table", required=True, metavar="KMER_LEVELS_TSV",
+                    help="The level table: the kmer_levels.tsv of `squiggle --kmer` on a run of the same chemistry.")
+    lo.add_argument("-o", "--output", required=True, help="Folder located.tsv and locate_report.json are written to.")
+    lo.add_argument("--table-min-events", dest="table_min_events", type=int, default=5,
+                    help="Fewest events a k-mer of the table must have for its level to be used.")
+    lo.add_argument("--skip", type=int, default=0, help="Samples left out at the start of every read.")
+    lo.add_argument("--prefix", type=int, default=2000,
+                    help="Samples of every read that are placed (at most 16384).  A few hundred are too few: the margins go to 0.")
+    lo.add_argument("--min-samples", dest="min_samples", type=int, default=200, help="A read with fewer samples after --skip is dropped.")
+    lo.add_argument("--normalize", default="mad", choices=["mad", "none"],
+                    help="mad: (x - median) / MAD of the prefix in 1/256 units, as squiggle normalises a read; none: the samples as they are.")
+    lo.add_argument("--max-cost", dest="max_cost", type=float, default=None,
+                    help="A read whose cost per sample, in 1/256 units, is above this is unplaced (default: no limit; not tuned on real reads).")
+    lo.add_argument("--min-margin", dest="min_margin", type=float, default=1.0,
+                    help="A read whose second-best locus costs less than this more per sample is ambiguous (not tuned on real reads).")
+    lo.add_argument("--targets", default=None, metavar="CONTIG:START-END,...",
+                    help="Regions (1-based, inclusive; a bare contig is all of it): located.tsv says on_target / off_target.")
+    lo.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one call, MiB.")
+    lo.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    lo.set_defaults(func=locate)
     return parser
 
 

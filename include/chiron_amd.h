@@ -415,7 +415,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  * Caller's memory.  This holds for every call below that takes a workspace, a tape or a device output buffer from its caller --
  * chiron_ctc_loss, chiron_rnn_train_forward / _backward, chiron_cnn_train_forward / _backward, chiron_align_pairs,
  * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_seed_candidates, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
- * chiron_pileup, chiron_signal_levels and chiron_signal_refine; their own comments say "uninitialised" or name the size function and mean this:
+ * chiron_pileup, chiron_signal_levels, chiron_signal_refine and chiron_signal_locate; their own comments say "uninitialised" or name the size function and mean this:
  *   - workspace, tape and output buffers may hold anything on entry: the results do not depend on it (the library clears what it
  *     needs cleared, on the call's stream);
  *   - every element of every output is written, the rows and frames that carry no result included (frames past seq_len, skipped and
@@ -424,7 +424,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *   - nothing outside the bytes that the call's *_workspace_size / *_train_sizes function names, and outside the outputs' own
  *     extents, is read or written: a caller may pack other data right behind a workspace of exactly that size.
  * tests/test_gpu_workspace.py holds every one of these calls to the three parts (chiron_signal_levels: tests/test_gpu_squiggle.py; chiron_signal_refine:
- * tests/test_gpu_refine.py). */
+ * tests/test_gpu_refine.py; chiron_signal_locate: tests/test_gpu_locate.py). */
 #define CHIRON_CTC_WANT_GRAD 1u
 #define CHIRON_CTC_TRUSTED 2u   /* chiron_ctc_loss: the caller has checked seq_len / labels / label_len: no read-back, no sync */
 #define CHIRON_CTC_MAX_T 8192
@@ -1048,6 +1048,66 @@ chiron_status chiron_signal_refine_workspace_size(int64_t items, int64_t samples
 chiron_status chiron_signal_refine(int32_t device_id, const int16_t* samples, const int64_t* sample_off, const int32_t* level,
                                    const int32_t* start_in, const int64_t* base_off, int64_t items, uint32_t flags, int32_t* start_out,
                                    int64_t* cost_out, void* workspace, void* stream);
+
+/* Signal location: where on a reference of expected levels a stretch of raw samples comes from, without calling its bases, by an
+ * exact subsequence dynamic-time-warping DP of the samples against every column of the reference (`locate`: the expected levels of
+ * both strands of a genome under a k-mer level table, the first few thousand samples of a read).
+ *
+ * A call has one reference and `items` queries.
+ *   Reference: ref_len int32 levels e[0 .. R), each inside -32767 .. 32767 or CHIRON_LOCATE_BREAK.  No path may use a break
+ *     column: breaks separate contigs and strands and stand for k-mers without a level.
+ *   Query i: Q_i = sample_off[i+1] - sample_off[i] int16 samples x, samples[sample_off[i] ..), 1 <= Q_i <= CHIRON_LOCATE_MAX_QUERY,
+ *     which keeps every real cost below 2^30: the DP is 32-bit.
+ *   Path: it assigns every sample t a column j_t with j_{t+1} in {j_t, j_t + 1}; the first and the last column are free.  A sample
+ *     stays on a base or moves to the next one; every base on the path gets at least one sample (chiron_signal_refine's premise).
+ *   Cost: the sum over t of |x[t] - e[j_t]|.
+ *   Per end column j: D[j] is the least cost of a path that ends at j, S[j] the smallest first column among the paths that attain
+ *     it.  As a recurrence over pairs ordered lexicographically (cost, then start):
+ *       (D, S)[0][j] = (|x[0] - e[j]|, j),
+ *       (D, S)[t][j] = lexmin((D, S)[t-1][j], (D, S)[t-1][j-1]) + (|x[t] - e[j]|, 0),
+ *     and a break column, or a column with no path, holds no value.
+ *   Output: for every item and every block b of CHIRON_LOCATE_BLOCK consecutive columns three int32 -- the least D[j] of the
+ *     block, the smallest j that attains it, and S[j] -- or CHIRON_LOCATE_NONE in all three for a block without a path.  The
+ *     blocks are part of the definition, not of the kernel: the host derives best and second-best loci from them.
+ * Everything is an integer, so the result is a property of the inputs.
+ *
+ * locate_kernel (csrc/locate.hip): row t needs only row t-1, so the rows are cut into chunks of CHIRON_LOCATE_CHUNK and one launch
+ * runs one chunk of every item; an item's DP row, (cost, start) a column, lives in the workspace between launches in two buffers
+ * that are swapped each launch.  A wave takes one (item, tile of 1024 columns), the units dealt to the launch's waves in a loop,
+ * CHIRON_LOCATE_THREADS / 64 waves a workgroup and at most CHIRON_LOCATE_MAX_GROUPS workgroups.  A lane keeps 16 consecutive
+ * columns and their levels in registers and one column of a halo of 64 columns left of the tile; a row's sample is wave-uniform,
+ * a lane's column 0 takes its left neighbour's last column by a DPP wave shift.  After r rows of a launch the halo is right from
+ * its column r on, so every owned column is right after all 64; only owned columns are stored.  An item whose rows end inside a
+ * launch reduces its tiles to the block triples there; no wave waits for another.  Every offset is 64-bit.
+ *
+ * Workspace (device memory), each part rounded up to 256 bytes: the offsets (8 bytes an item + 8), 2 bytes a sample, 4 bytes a
+ * column of levels, 12 bytes an item and block of triples, and two arrays of 8 bytes an item and column of ceil(ref_len / 1024) *
+ * 1024 columns (cost and start, for the two buffers).  It depends on the three counts only.  Host-only.  CHIRON_ERR_INVALID: a negative
+ * argument.  CHIRON_ERR_OVERFLOW: items > 2^31 - 1, samples > CHIRON_SIGNAL_MAX_SAMPLES, ref_len > CHIRON_LOCATE_MAX_REF, more
+ * than CHIRON_LOCATE_MAX_CELLS row cells (items times those columns).                                                           */
+#define CHIRON_LOCATE_BREAK INT32_MIN     /* a level: no path may use this column */
+#define CHIRON_LOCATE_NONE INT32_MAX      /* all three of a block's triple: no path ends in it */
+#define CHIRON_LOCATE_MAX_QUERY 16384     /* samples of a query: 16384 * 65534 < 2^30 */
+#define CHIRON_LOCATE_BLOCK 1024          /* columns of a block of the output */
+#define CHIRON_LOCATE_MAX_REF (1 << 28)   /* columns of a reference */
+#define CHIRON_LOCATE_MAX_CELLS (1ll << 40)
+#define CHIRON_LOCATE_CHUNK 64            /* rows a launch */
+#define CHIRON_LOCATE_THREADS 256
+#define CHIRON_LOCATE_MAX_GROUPS 2048
+chiron_status chiron_signal_locate_workspace_size(int64_t items, int64_t samples, int64_t ref_len, size_t* bytes);
+
+/* Locates `items` queries on one reference.  samples, sample_off (int64 [items + 1], non-negative, increasing) and ref_level
+ * (int32 [ref_len]) are HOST memory.  Output, HOST memory: block_out int32 [items][ceil(ref_len / CHIRON_LOCATE_BLOCK)][3].
+ * workspace: device memory on device_id of at least the size function's bytes for (items, the call's samples, ref_len) ("Caller's
+ * memory" above); workspace_bytes says how many it has.  flags: 0 (reserved).  Copies the inputs in, runs ceil(longest query /
+ * CHIRON_LOCATE_CHUNK) launches of locate_kernel on `stream` (a hipStream_t; NULL = the null stream) and synchronises it before
+ * returning.  CHIRON_ERR_INVALID: unknown flags, a negative count, a null array that is needed, a negative or decreasing offset,
+ * an empty query, a level outside -32767 .. 32767 that is not CHIRON_LOCATE_BREAK, a workspace smaller than needed.
+ * CHIRON_ERR_OVERFLOW: a query above CHIRON_LOCATE_MAX_QUERY, and as the size function.  All of it before anything is copied or
+ * launched.  items == 0 touches no device and writes nothing; ref_len == 0 touches no device either and has no block to fill.    */
+chiron_status chiron_signal_locate(int32_t device_id, const int16_t* samples, const int64_t* sample_off, int64_t items,
+                                   const int32_t* ref_level, int64_t ref_len, int32_t* block_out, void* workspace, size_t workspace_bytes,
+                                   uint32_t flags, void* stream);
 
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
