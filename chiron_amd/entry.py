@@ -674,7 +674,7 @@ def build_parser():
                     help="Fewest events a k-mer of the table must have for its level to be used.")
     lo.add_argument("--skip", type=int, default=0, help="Samples left out at the start of every read.")
     lo.add_argument("--prefix", type=int, default=2000,
-                    help="Samples of every read that are placed (at most 16384).  A few hundred are too few: the margins go to 0.")
+                    help="Samples of every read that are placed (at most 16384, or 131072 under --events).  A few hundred are too few: the margins go to 0.")
     lo.add_argument("--min-samples", dest="min_samples", type=int, default=200, help="A read with fewer samples after --skip is dropped.")
     lo.add_argument("--normalize", default="mad", choices=["mad", "none"],
                     help="mad: (x - median) / MAD of the prefix in 1/256 units, as squiggle normalises a read; none: the samples as they are.")
@@ -684,6 +684,17 @@ def build_parser():
                     help="A read whose second-best locus costs less than this more per sample is ambiguous (not tuned on real reads).")
     lo.add_argument("--targets", default=None, metavar="CONTIG:START-END,...",
                     help="Regions (1-based, inclusive; a bare contig is all of it): located.tsv says on_target / off_target.")
+    lo.add_argument("--events", action="store_true",
+                    help="Cut the prefix into events of one level each and place the events, by a DTW whose path may skip a base: "
+                    "--prefix may then be up to 131072, a read keeps at most 8192 events, and costs and margins are per event.")
+    lo.add_argument("--event-window", dest="event_window", type=int, default=3,
+                    help="--events: samples on either side of a border that the t statistic compares, 2 to 16 (not tuned on real reads).")
+    lo.add_argument("--event-threshold", dest="event_threshold", type=float, default=3.0,
+                    help="--events: the least t^2 of a border (not tuned on real reads).")
+    lo.add_argument("--event-radius", dest="event_radius", type=int, default=2,
+                    help="--events: a border is the peak of the statistic within this many samples, 1 to 16 (not tuned on real reads).")
+    lo.add_argument("--skip-penalty", dest="skip_penalty", type=int, default=150,
+                    help="--events: what a base without an event costs, in 1/256 units, 0 to 65534 (not tuned on real reads).")
     lo.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one call, MiB.")
     lo.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     lo.set_defaults(func=locate)

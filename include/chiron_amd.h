@@ -415,7 +415,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  * Caller's memory.  This holds for every call below that takes a workspace, a tape or a device output buffer from its caller --
  * chiron_ctc_loss, chiron_rnn_train_forward / _backward, chiron_cnn_train_forward / _backward, chiron_align_pairs,
  * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_seed_candidates, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
- * chiron_pileup, chiron_signal_levels, chiron_signal_refine and chiron_signal_locate; their own comments say "uninitialised" or name the size function and mean this:
+ * chiron_pileup, chiron_signal_levels, chiron_signal_refine, chiron_signal_locate and chiron_event_locate; their own comments say "uninitialised" or name the size function and mean this:
  *   - workspace, tape and output buffers may hold anything on entry: the results do not depend on it (the library clears what it
  *     needs cleared, on the call's stream);
  *   - every element of every output is written, the rows and frames that carry no result included (frames past seq_len, skipped and
@@ -424,7 +424,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *   - nothing outside the bytes that the call's *_workspace_size / *_train_sizes function names, and outside the outputs' own
  *     extents, is read or written: a caller may pack other data right behind a workspace of exactly that size.
  * tests/test_gpu_workspace.py holds every one of these calls to the three parts (chiron_signal_levels: tests/test_gpu_squiggle.py; chiron_signal_refine:
- * tests/test_gpu_refine.py; chiron_signal_locate: tests/test_gpu_locate.py). */
+ * tests/test_gpu_refine.py; chiron_signal_locate: tests/test_gpu_locate.py; chiron_event_locate: tests/test_gpu_event_locate.py). */
 #define CHIRON_CTC_WANT_GRAD 1u
 #define CHIRON_CTC_TRUSTED 2u   /* chiron_ctc_loss: the caller has checked seq_len / labels / label_len: no read-back, no sync */
 #define CHIRON_CTC_MAX_T 8192
@@ -1108,6 +1108,72 @@ chiron_status chiron_signal_locate_workspace_size(int64_t items, int64_t samples
 chiron_status chiron_signal_locate(int32_t device_id, const int16_t* samples, const int64_t* sample_off, int64_t items,
                                    const int32_t* ref_level, int64_t ref_len, int32_t* block_out, void* workspace, size_t workspace_bytes,
                                    uint32_t flags, void* stream);
+
+/* Event detection: cuts raw samples into events of one level each, so that a location DP has one row an event and not one a
+ * sample (`locate --events`).  Host-only, all in integers (csrc/event_pack.h); O(samples), no kernel and no device.
+ *
+ * Item i is n = sample_off[i+1] - sample_off[i] int16 samples x, 1 <= n <= CHIRON_EVENT_MAX_SAMPLES.  With a window w in 2 .. 16,
+ * a radius r in 1 .. 16 and a threshold thr in 1 .. CHIRON_EVENT_MAX_THRESHOLD:
+ *   For w <= i <= n - w: S1, Q1 are the sum and the sum of squares of x[i-w .. i), S2, Q2 those of x[i .. i+w), d = S1 - S2,
+ *     V = (w Q1 - S1^2) + (w Q2 - S2^2), and T[i] = (w d^2 256) / max(V, 1), floor division: 256 times Welch's t^2 for two windows
+ *     of equal size with population variances.  w d^2 256 <= 16 (16 * 65535)^2 256 < 2^52, so int64 holds it.
+ *   T[i] = 0 for every other i of 0 .. n.
+ *   i is a border iff T[i] >= thr and i is the first index of the maximum of T over [max(i-r, 0), min(i+r, n)], both ends
+ *     included; 0 and n are always borders.
+ *   Event k spans the samples between border k and border k+1; its level is floor((2 s + c) / (2 c)) of their sum s and count c
+ *     (chiron_signal_levels' rounding: the mean, halves up).
+ *   At most max_events (1 .. CHIRON_EVENT_MAX_SAMPLES) events are kept, the first ones, and truncated_out[i] says whether any
+ *     was dropped: the last kept event still ends at its own border.
+ * Outputs, HOST memory: count_out int32 [items]; border_out int32, item i's count_i + 1 borders (sample indices inside the item,
+ * the first 0) from index sample_off[i] - sample_off[0] + i on, so the array has (samples of the call + items) entries;
+ * level_out int16, item i's count_i levels from index sample_off[i] - sample_off[0] on (samples of the call entries);
+ * truncated_out uint8 [items].  Entries past an item's count are left as they were.
+ * CHIRON_ERR_INVALID: unknown flags (0 is the only value), a negative count, a null array that is needed, a negative or decreasing
+ * offset, an empty item, w, r, thr or max_events out of range.  CHIRON_ERR_OVERFLOW: items > 2^31 - 1, an item above
+ * CHIRON_EVENT_MAX_SAMPLES.  All of it before anything is written.  items == 0 writes nothing.                                    */
+#define CHIRON_EVENT_MAX_SAMPLES (1 << 17)       /* samples of one item */
+#define CHIRON_EVENT_MAX_WINDOW 16
+#define CHIRON_EVENT_MAX_RADIUS 16
+#define CHIRON_EVENT_MAX_THRESHOLD (1ll << 52)
+chiron_status chiron_signal_events(const int16_t* samples, const int64_t* sample_off, int64_t items, int32_t window, int32_t radius,
+                                   int64_t threshold, int32_t max_events, uint32_t flags, int32_t* count_out, int32_t* border_out,
+                                   int16_t* level_out, uint8_t* truncated_out);
+
+/* Event location: chiron_signal_locate's question for a query of event levels, whose detector may have missed a border and so left
+ * a base without an event.  Everything is as in chiron_signal_locate -- reference, break columns, blocks, the triples -- except:
+ *   Query i: Q_i = event_off[i+1] - event_off[i] int16 levels x, 1 <= Q_i <= CHIRON_EVENT_MAX_QUERY = 8192.
+ *   Path: j_{t+1} in {j_t, j_t + 1, j_t + 2}; the move by 2 skips column j_t + 1, costs `penalty` P on top, 0 <= P <=
+ *     CHIRON_EVENT_MAX_PENALTY = 65534, and is not allowed when the skipped column is a break: no path crosses a break.
+ *   Recurrence:
+ *       (D, S)[0][j] = (|x[0] - e[j]|, j),
+ *       (D, S)[t][j] = lexmin((D, S)[t-1][j], (D, S)[t-1][j-1], (D, S)[t-1][j-2] + (P, 0) only if e[j-1] is not a break)
+ *                      + (|x[t] - e[j]|, 0).
+ *   A row adds at most 65535 + 65534, and 8192 * (65535 + 65534) < 2^30, which keeps every real cost below 2^30: the DP is 32-bit.
+ *
+ * event_locate_kernel (csrc/event_locate.hip) has locate_kernel's form: a wave per (item, tile of 1024 columns), 16 columns a lane
+ * in registers, packed 64-bit (cost, start) words, CHIRON_EVENT_CHUNK = 64 rows a launch with the row in the workspace between
+ * launches in two swapped buffers.  A path moves up to two columns a row, so the halo is 128 columns, two a lane: after r rows of a
+ * launch it is right from its column 2 r on, and an owned column reads its last two columns of row r - 1, right for r <= 64.  A
+ * lane's columns 0 and 1 take the old columns 15 and 14 of its left neighbour by two DPP wave shifts.
+ *
+ * Workspace: as chiron_signal_locate_workspace_size with events for samples; the same refusals.                                  */
+#define CHIRON_EVENT_MAX_QUERY 8192       /* events of a query: 8192 * (65535 + 65534) < 2^30 */
+#define CHIRON_EVENT_MAX_PENALTY 65534
+#define CHIRON_EVENT_CHUNK 64             /* rows a launch */
+#define CHIRON_EVENT_HALO 128             /* columns left of a tile that a launch recomputes: 2 a row */
+chiron_status chiron_event_locate_workspace_size(int64_t items, int64_t events, int64_t ref_len, size_t* bytes);
+
+/* Locates `items` queries of events on one reference.  events, event_off (int64 [items + 1], non-negative, increasing) and
+ * ref_level (int32 [ref_len]) are HOST memory.  Output, HOST memory: block_out int32 [items][ceil(ref_len / CHIRON_LOCATE_BLOCK)][3].
+ * workspace: device memory on device_id of at least the size function's bytes for (items, the call's events, ref_len) ("Caller's
+ * memory" above, tests/test_gpu_event_locate.py); workspace_bytes says how many it has.  flags: 0 (reserved).  Copies the inputs in,
+ * runs ceil(longest query / CHIRON_EVENT_CHUNK) launches of event_locate_kernel on `stream` (a hipStream_t; NULL = the null stream)
+ * and synchronises it before returning.  CHIRON_ERR_INVALID: as chiron_signal_locate, and a penalty outside 0 ..
+ * CHIRON_EVENT_MAX_PENALTY.  CHIRON_ERR_OVERFLOW: a query above CHIRON_EVENT_MAX_QUERY, and as the size function.  All of it before
+ * anything is copied or launched.  items == 0 touches no device and writes nothing; ref_len == 0 touches no device either.        */
+chiron_status chiron_event_locate(int32_t device_id, const int16_t* events, const int64_t* event_off, int64_t items,
+                                  const int32_t* ref_level, int64_t ref_len, int32_t penalty, int32_t* block_out, void* workspace,
+                                  size_t workspace_bytes, uint32_t flags, void* stream);
 
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
