@@ -39,6 +39,7 @@ LOCATE_BREAK, LOCATE_NONE, LOCATE_MAX_QUERY, LOCATE_BLOCK, LOCATE_MAX_REF, LOCAT
 LOCATE_CHUNK, LOCATE_THREADS, LOCATE_MAX_GROUPS = 64, 256, 2048
 EVENT_MAX_SAMPLES, EVENT_MAX_WINDOW, EVENT_MAX_RADIUS, EVENT_MAX_THRESHOLD = 1 << 17, 16, 16, 1 << 52
 EVENT_MAX_QUERY, EVENT_MAX_PENALTY, EVENT_CHUNK, EVENT_HALO = 8192, 65534, 64, 128
+SITE_MAX_SAMPLES, SITE_MAX_COLUMNS, SITE_INFEASIBLE, SITE_THREADS, SITE_MAX_GROUPS = 4096, 16, (1 << 31) - 1, 256, 2048
 PILEUP_INS_SLOTS, PILEUP_MAX_COLUMNS, PILEUP_MAX_TILE, PILEUP_THREADS = 4, 1 << 24, 1 << 28, 256
 PILEUP_PLANES = 6 + 5 * PILEUP_INS_SLOTS + 1
 PILEUP_CHUNK = 4 * PILEUP_THREADS    # columns a workgroup of csrc/pileup.hip loads before it scans them, 256 at a time
@@ -195,6 +196,9 @@ SYMBOLS = [
     ("chiron_event_locate_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     ("chiron_event_locate", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_uint32, C.c_void_p]),
+    ("chiron_signal_score_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    ("chiron_signal_score", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_uint32, C.c_void_p]),
     ("chiron_last_error", C.c_char_p, []),
     ("chiron_device_pci_bus_id", C.c_int, [C.c_int32, C.c_char_p, C.c_size_t]),
     ("chiron_abi_version", C.c_int32, []),

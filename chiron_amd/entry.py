@@ -369,6 +369,25 @@ def locate(args):
     return report
 
 
+def modcall(args):
+    """Per-read calls of modified bases at motif sites: modcall.modcall_command (every read's samples around every motif group fitted
+    to the window's levels under a canonical and under a modified k-mer level table, by an exact DTW on the GPU).  Writes
+    <out>/mod_calls.tsv, <out>/mod_sites.tsv and <out>/modcall_report.json; exits non-zero on a file that is no level table, on two
+    tables of different k, on an input without a mapped.sam or when no read could be used."""
+    from . import modcall as modcall_mod
+    try:
+        report = modcall_mod.modcall_command(args)
+    except ValueError as e:
+        sys.exit("modcall: %s" % e)
+    c = report["calls"]
+    print("modcall: %d of %d reads used; %d of %d (read, group) pairs scored in %d calls; %d modified, %d canonical, %d ambiguous at %d sites; wrote %s"
+          % (report["reads"]["used"], report["reads"]["total"], report["groups"]["scored"], report["groups"]["seen"], report["batches"], c["modified"],
+             c["canonical"], c["ambiguous"], report["sites"], ", ".join(report["files"])))
+    if report["reads"]["used"] == 0:
+        sys.exit("modcall: no read of %s could be used (%s)" % (report["sam"], report["reads"]["dropped"]))
+    return report
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="chiron", description="A deep neural network basecaller (MI355X engine).")
     parser.add_argument("-v", "--version", action="version", version="chiron_amd version " + __version__)
@@ -698,6 +717,44 @@ def build_parser():
     lo.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one call, MiB.")
     lo.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     lo.set_defaults(func=locate)
+    mc = subparsers.add_parser("modcall", description="Call modified bases per read: at every motif site of every mapped read, the samples "
+                               "around the site against the window's expected levels under a canonical and under a modified k-mer level "
+                               "table, by an exact dynamic time warping with free borders on the GPU; the difference of the two costs is "
+                               "the call",
+                               help="Per-read modified-base calls at motif sites from two k-mer level tables.")
+    mc.add_argument("-i", "--input", required=True, help="Output folder of `map --cigar` (its mapped.sam is read), or a SAM file.")
+    mc.add_argument("-s", "--signal", required=True, help="Output folder of `call` (its raw/ is read), or a folder of .signal files.")
+    mc.add_argument("-g", "--genome", required=True, help="The genome FASTA the reads were mapped to.")
+    mc.add_argument("-m", "--model", type=str, default=model_default_path, help="model folder path")
+    mc.add_argument("--table", required=True, metavar="KMER_LEVELS_TSV",
+                    help="The canonical level table: the kmer_levels.tsv of `squiggle --kmer` on an unmodified run.")
+    mc.add_argument("--alt-table", dest="alt_table", required=True, metavar="KMER_LEVELS_TSV",
+                    help="The alternative level table: the same command on a fully modified run; it must have the same k.")
+    mc.add_argument("-o", "--output", required=True, help="Folder mod_calls.tsv, mod_sites.tsv and modcall_report.json are written to.")
+    mc.add_argument("--motif", default="CG", help="The motif, over ACGT; on the reverse strand its occurrences in the reverse complement.")
+    mc.add_argument("--motif-offset", dest="motif_offset", type=int, default=0, help="Which base of the motif is the modified one, from 0.")
+    mc.add_argument("--flank", type=int, default=2,
+                    help="Positions the window extends past the k-mers around a group's first and last site; a window above 16 is dropped.")
+    mc.add_argument("--min-delta", dest="min_delta", type=float, default=8.0,
+                    help="A (read, group) whose costs differ by at least this much per sample, in 1/256 units, is called modified or "
+                         "canonical, anything else ambiguous (from a sketch on planted reads; not tuned on real reads).")
+    mc.add_argument("--table-min-events", dest="table_min_events", type=int, default=5,
+                    help="Fewest events a k-mer of either table must have for its level to be used.")
+    mc.add_argument("--min-mapq", dest="min_mapq", type=int, default=0,
+                    help="Drop alignments whose MAPQ is below this (`map --candidates` writes one; 255, not available, always passes).")
+    mc.add_argument("--normalize", default="mad", choices=["mad", "none"],
+                    help="mad: per read, (x - median) / MAD in 1/256 units, as squiggle normalises; none: the samples as they are, rounded.")
+    mc.add_argument("-l", "--segment_len", type=int, default=400, help="Window length; the windows do not overlap.")
+    mc.add_argument("-b", "--batch_size", type=int, default=1100, help="Windows per engine batch.")
+    mc.add_argument("--band", type=int, default=256, help="First half-width of the frame alignment's band, in CTC states; 0: the full table.")
+    mc.add_argument("--max-band", dest="max_band", type=int, default=8192,
+                    help="Largest half-width the doubling may reach before a read is given up (0: unbounded).")
+    mc.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one call of any stage, MiB.")
+    mc.add_argument("--dtype", default="fp32", choices=["fp32", "fp16", "fp16-w2", "fp32-split"], help="Engine arithmetic.")
+    mc.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    mc.add_argument("--synthetic-weights", dest="synthetic_weights", action="store_true",
+                    help="Use seeded synthetic weights when the model folder has no checkpoint data.")
+    mc.set_defaults(func=modcall)
     return parser
 
 

@@ -415,7 +415,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  * Caller's memory.  This holds for every call below that takes a workspace, a tape or a device output buffer from its caller --
  * chiron_ctc_loss, chiron_rnn_train_forward / _backward, chiron_cnn_train_forward / _backward, chiron_align_pairs,
  * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_seed_candidates, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
- * chiron_pileup, chiron_signal_levels, chiron_signal_refine, chiron_signal_locate and chiron_event_locate; their own comments say "uninitialised" or name the size function and mean this:
+ * chiron_pileup, chiron_signal_levels, chiron_signal_refine, chiron_signal_locate, chiron_event_locate and chiron_signal_score; their own comments say "uninitialised" or name the size function and mean this:
  *   - workspace, tape and output buffers may hold anything on entry: the results do not depend on it (the library clears what it
  *     needs cleared, on the call's stream);
  *   - every element of every output is written, the rows and frames that carry no result included (frames past seq_len, skipped and
@@ -424,7 +424,8 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *   - nothing outside the bytes that the call's *_workspace_size / *_train_sizes function names, and outside the outputs' own
  *     extents, is read or written: a caller may pack other data right behind a workspace of exactly that size.
  * tests/test_gpu_workspace.py holds every one of these calls to the three parts (chiron_signal_levels: tests/test_gpu_squiggle.py; chiron_signal_refine:
- * tests/test_gpu_refine.py; chiron_signal_locate: tests/test_gpu_locate.py; chiron_event_locate: tests/test_gpu_event_locate.py). */
+ * tests/test_gpu_refine.py; chiron_signal_locate: tests/test_gpu_locate.py; chiron_event_locate: tests/test_gpu_event_locate.py;
+ * chiron_signal_score: tests/test_gpu_modcall.py). */
 #define CHIRON_CTC_WANT_GRAD 1u
 #define CHIRON_CTC_TRUSTED 2u   /* chiron_ctc_loss: the caller has checked seq_len / labels / label_len: no read-back, no sync */
 #define CHIRON_CTC_MAX_T 8192
@@ -1174,6 +1175,59 @@ chiron_status chiron_event_locate_workspace_size(int64_t items, int64_t events, 
 chiron_status chiron_event_locate(int32_t device_id, const int16_t* events, const int64_t* event_off, int64_t items,
                                   const int32_t* ref_level, int64_t ref_len, int32_t penalty, int32_t* block_out, void* workspace,
                                   size_t workspace_bytes, uint32_t flags, void* stream);
+
+/* Site scoring: how well a short stretch of samples fits each of several short rows of expected levels, both ends fixed, by an
+ * exact dynamic-time-warping DP (`modcall`: a read's samples around a motif site against the window's levels under a canonical
+ * and under a modified k-mer level table; the difference of the two costs is the call).
+ *
+ * A call has `segments` sample stretches and `candidates` level rows; many candidates may share one segment, as in
+ * chiron_ctc_score.
+ *   Segment g: S_g = sample_off[g+1] - sample_off[g] int16 samples x, samples[sample_off[g] ..), 0 <= S_g <= CHIRON_SITE_MAX_SAMPLES.
+ *   Candidate c: names a segment seg[c] in 0 .. segments - 1 and has L_c = level_off[c+1] - level_off[c] int32 levels e =
+ *     level[level_off[c] ..), each inside -32767 .. 32767, 1 <= L_c <= CHIRON_SITE_MAX_COLUMNS.  Candidates come in any order, several
+ *     may name one segment, a segment may have none.
+ *   Path: it assigns sample t of the segment a column j_t with j_0 = 0, j_{S-1} = L - 1 and j_{t+1} in {j_t, j_t + 1}: both ends are
+ *     fixed and every column gets at least one sample (chiron_signal_refine's premise).
+ *   cost[c] = min over the paths of the sum over t of |x[t] - e[j_t]|, an int32: at most 4096 * 65535 < 2^29.  It is
+ *     CHIRON_SITE_INFEASIBLE when there is no path: S < L, S = 0 included.
+ *   As a recurrence: D[0][0] = |x[0] - e[0]|, D[0][n] has no value for n > 0, D[t][n] = min(D[t-1][n], D[t-1][n-1]) + |x[t] - e[n]|
+ *     over the terms that have a value, and cost = D[S-1][L-1].
+ * Everything is an integer, so the result is a property of the inputs.  No path is returned and no start column: a caller wants
+ * one number a candidate.
+ *
+ * site_kernel (csrc/site_score.hip): a lane a candidate, the candidates dealt 64 at a time to the launch's waves in a loop,
+ * CHIRON_SITE_THREADS / 64 waves a workgroup and at most CHIRON_SITE_MAX_GROUPS workgroups.  A lane keeps its 16 columns and 16
+ * levels in registers, samples and levels biased by 32768 to unsigned; columns without a path hold 2^30 and need no clamp (2^30 +
+ * 4096 * 65535 < 2^31).  A row updates the columns from the highest down; columns at and above L_c are computed and ignored, a
+ * lane past its own S keeps its row, and column L_c - 1 is picked once at the end.  The samples go through a wave-private slice of
+ * LDS in pieces of 64 a segment: every distinct segment among the wave's 64 candidates is loaded once a piece, a sample a lane,
+ * into a row of its own; rows are 33 words apart, so two rows share a bank only when they are 32 rows apart, and lanes of one
+ * segment read one address.  No workgroup barrier.  Every offset is 64-bit.
+ *
+ * Workspace (device memory), each part rounded up to 256 bytes: the segment offsets (8 bytes a segment + 8), the samples (2 bytes
+ * a sample + 16, so that a 16-byte load that starts inside them ends inside them), the level offsets (8 bytes a candidate + 8), 4
+ * bytes a level, 4 bytes a candidate of segment indices and 4 bytes a candidate of costs.  It depends on the four counts only.
+ * Host-only.  CHIRON_ERR_INVALID: a negative argument.  CHIRON_ERR_OVERFLOW: segments > 2^31 - 1, samples >
+ * CHIRON_SIGNAL_MAX_SAMPLES, candidates > 2^31 - 1, levels > 2^31 - 1.                                                          */
+#define CHIRON_SITE_MAX_SAMPLES 4096      /* samples of a segment: 4096 * 65535 < 2^30 */
+#define CHIRON_SITE_MAX_COLUMNS 16        /* levels of a candidate: a lane's registers */
+#define CHIRON_SITE_INFEASIBLE INT32_MAX
+#define CHIRON_SITE_THREADS 256
+#define CHIRON_SITE_MAX_GROUPS 2048
+chiron_status chiron_signal_score_workspace_size(int64_t segments, int64_t samples, int64_t candidates, int64_t levels, size_t* bytes);
+
+/* Scores `candidates` candidates on `segments` segments in one launch.  samples, sample_off (int64 [segments + 1]), level, level_off
+ * (int64 [candidates + 1]) and seg (int32 [candidates]) are HOST memory, the offsets non-negative and non-decreasing.  Output, HOST
+ * memory: cost_out int32 [candidates].  workspace: device memory on device_id of at least the size function's bytes for (segments,
+ * the call's samples, candidates, the call's levels) ("Caller's memory" above); workspace_bytes says how many it has.  flags: 0
+ * (reserved).  Copies the inputs in, runs site_kernel on `stream` (a hipStream_t; NULL = the null stream) and synchronises it
+ * before returning.  CHIRON_ERR_INVALID: unknown flags, a negative count, a null array that is needed, a negative or decreasing
+ * offset, a segment above CHIRON_SITE_MAX_SAMPLES, a candidate with no level or more than CHIRON_SITE_MAX_COLUMNS, a seg entry
+ * outside 0 .. segments - 1, a level outside -32767 .. 32767, a null workspace or one smaller than needed.  CHIRON_ERR_OVERFLOW: as
+ * the size function.  All of it before anything is copied or launched.  candidates == 0 touches no device and writes nothing.   */
+chiron_status chiron_signal_score(int32_t device_id, const int16_t* samples, const int64_t* sample_off, int64_t segments,
+                                  const int32_t* level, const int64_t* level_off, const int32_t* seg, int64_t candidates,
+                                  int32_t* cost_out, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
 
 const char* chiron_last_error(void);
 int32_t chiron_abi_version(void);
