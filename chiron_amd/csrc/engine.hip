@@ -1317,7 +1317,6 @@ extern "C" chiron_status chiron_engine_features(chiron_engine* e, int32_t slot, 
   if (s->state.v.load(std::memory_order_acquire) != 0) return fail(CHIRON_ERR_STATE, "slot %d holds an uncollected batch", slot);
   if (s->net_batch < 1 || s->sig_used == nullptr)
     return fail(CHIRON_ERR_STATE, "slot %d holds no network batch (nothing submitted yet, or its last batch was decode-only)", slot);
-  if (e->split) return fail(CHIRON_ERR_INVALID, "chiron_engine_features: dtype fp32-split keeps features as hi/lo half pairs; not exported");
   const size_t n = (size_t)s->net_batch * e->T * e->C;
   if (out_batch) *out_batch = s->net_batch;
   if (out_channels) *out_channels = e->C;
@@ -1328,6 +1327,14 @@ extern "C" chiron_status chiron_engine_features(chiron_engine* e, int32_t slot, 
     std::vector<_Float16> h(n);
     HIP_TRY(hipMemcpy(h.data(), s->sig_used, n * 2, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) out[i] = (float)h[i];
+  } else if (e->split) {
+    // hi + lo half pairs, per 32-element block of a row 32 hi halves then 32 lo halves (gemm.hip's split epilogue; C is a multiple of 128)
+    std::vector<_Float16> h(2 * n);
+    HIP_TRY(hipMemcpy(h.data(), s->sig_used, n * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+      const size_t at = (i / 32) * 64 + i % 32;
+      out[i] = (float)h[at] + (float)h[at + 32];
+    }
   } else {
     HIP_TRY(hipMemcpy(out, s->sig_used, n * 4, hipMemcpyDeviceToHost));
   }

@@ -230,7 +230,7 @@ chiron_status chiron_engine_device_results(chiron_engine* e, int32_t slot, const
  * of the batch most recently run on `slot`, which must be idle (collected).  Copied into out [cap_floats];
  * *out_batch / *out_channels receive batch and C.  CHIRON_ERR_OVERFLOW when cap_floats is too small (the sizes are
  * still reported), CHIRON_ERR_STATE before the first batch or with a batch in flight.  Stage-level parity checks use
- * it (tests); dtype CHIRON_F32_SPLIT does not export its hi/lo pairs (CHIRON_ERR_INVALID).                       */
+ * it (tests); dtype CHIRON_F32_SPLIT returns hi + lo of its half pairs.                                          */
 chiron_status chiron_engine_features(chiron_engine* e, int32_t slot, float* out, size_t cap_floats, int32_t* out_batch,
                                      int32_t* out_channels);
 

@@ -153,8 +153,10 @@ def test_errors_through_the_abi(dna):
         assert f16.shape == fea.shape and np.abs(f16 - fea).max() < 0.05 * max(1.0, float(np.abs(fea).max()))
     with ca.Engine(spec, w, max_batch=8, segment_len=400, dtype="fp32-split") as es:
         es.infer(xs, ca.seq_len_for_engine(ls, es.ratio))
+        fs = es.features()                         # hi + lo of the half pairs (22 bits)
+        assert fs.shape == fea.shape and np.abs(fs - fea).max() < 1e-4 * max(1.0, float(np.abs(fea).max()))
         with pytest.raises(_lib.ChironError) as ei:
-            es.features()
+            es.rnn_output()                        # lasth stays unexported for this dtype
         assert ei.value.status == _lib.ERR_INVALID
 
 
