@@ -1,7 +1,7 @@
 // What `locate --events` does on the host, as plain C++ without HIP: the event detector of chiron_signal_events (the definition is in
-// include/chiron_amd.h and is restated in plain Python by tests/event_ref.py), and the walk over the queries' offsets that
-// chiron_event_locate checks them with before it copies anything.  The levels of the reference are walked by locate_pack.h.  Host-only
-// and free of the library's state, so that tests/native/event_pack_check.cpp can run it under a sanitizer.
+// include/chiron_amd.h and is restated in plain Python by tests/event_ref.py), and the caps chiron_event_locate holds its queries to.
+// The offsets and the levels of the reference are walked by locate_pack.h.  Host-only and free of the library's state, so that
+// tests/native/event_pack_check.cpp can run it under a sanitizer.
 #pragma once
 #include <stdint.h>
 
@@ -21,24 +21,7 @@ constexpr int64_t EVENT_CHUNK = 64;                  // CHIRON_EVENT_CHUNK: rows
 static_assert(EVENT_MAX_QUERY * (65535 + EVENT_MAX_PENALTY) < (1ll << 30), "every real cost is below 2^30: the DP is 32-bit");
 static_assert((int64_t)EVENT_MAX_WINDOW * (EVENT_MAX_WINDOW * 65535ll) * (EVENT_MAX_WINDOW * 65535ll) * 256 < (1ll << 52), "T's numerator is below 2^52");
 
-// off[0 .. items]: starts at or above 0, never decreases, every item has 1 .. limit entries.  The faults are locate_pack.h's; stops
-// at the first; *longest receives the longest item when there is none.  Reads nothing past off[items].
-inline LocateFinding event_check_offsets(const int64_t* off, int64_t items, int64_t limit, int64_t* longest) {
-  if (off[0] < 0) return {LOCATE_OFF_NEGATIVE, 0, off[0]};
-  int64_t most = 0;
-  for (int64_t i = 0; i < items; ++i) {
-    if (off[i + 1] < off[i]) return {LOCATE_OFF_ORDER, i + 1, off[i + 1]};
-    const int64_t q = off[i + 1] - off[i];   // both at or above 0: the difference stays inside int64
-    if (q == 0) return {LOCATE_QUERY_EMPTY, i, 0};
-    if (q > limit) return {LOCATE_QUERY_LONG, i, q};
-    if (q > most) most = q;
-  }
-  *longest = most;
-  return {LOCATE_FINE, 0, 0};
-}
-
-// launches a call needs: chunks of EVENT_CHUNK rows of its longest query
-inline int64_t event_launches(int64_t longest) { return (longest + EVENT_CHUNK - 1) / EVENT_CHUNK; }
+static_assert(EVENT_CHUNK == LOCATE_CHUNK, "locate_launches plans both calls");
 
 // floor((2 s + c) / (2 c)), c > 0: the mean with halves up, as chiron_signal_levels rounds
 inline int64_t event_level(int64_t s, int64_t c) {

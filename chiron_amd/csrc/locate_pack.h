@@ -16,7 +16,7 @@ static_assert(LOCATE_MAX_QUERY * 2 * LOCATE_LEVEL_MAX < (1ll << 30), "every real
 
 enum LocateFault { LOCATE_FINE = 0, LOCATE_OFF_NEGATIVE = 1, LOCATE_OFF_ORDER = 2, LOCATE_QUERY_EMPTY = 3, LOCATE_QUERY_LONG = 4, LOCATE_LEVEL_RANGE = 5 };
 
-// What a walk found wrong: `at` is the index into sample_off (OFF_*), the item (QUERY_*) or the column (LEVEL_RANGE), value what
+// What a walk found wrong: `at` is the index into the offsets (OFF_*), the item (QUERY_*) or the column (LEVEL_RANGE), value what
 // it holds there (the query's length for QUERY_*).
 struct LocateFinding {
   LocateFault fault;
@@ -24,17 +24,18 @@ struct LocateFinding {
   int64_t value;
 };
 
-// sample_off[0 .. items]: starts at or above 0, never decreases, every query has 1 .. LOCATE_MAX_QUERY samples.  Stops at the
-// first fault; *longest receives the longest query when there is none.  Reads nothing past sample_off[items].
-inline LocateFinding locate_check_offsets(const int64_t* sample_off, int64_t items, int64_t* longest) {
-  if (sample_off[0] < 0) return {LOCATE_OFF_NEGATIVE, 0, sample_off[0]};
+// off[0 .. items]: starts at or above 0, never decreases, every item has 1 .. limit entries (LOCATE_MAX_QUERY samples; for
+// event_pack.h's callers EVENT_MAX_QUERY events or EVENT_MAX_SAMPLES samples).  Stops at the first fault; *longest receives the
+// longest item when there is none.  Reads nothing past off[items].
+inline LocateFinding locate_check_offsets(const int64_t* off, int64_t items, int64_t limit, int64_t* longest) {
+  if (off[0] < 0) return {LOCATE_OFF_NEGATIVE, 0, off[0]};
   int64_t most = 0;
   for (int64_t i = 0; i < items; ++i) {
     // the difference of two int64 can leave int64 only when they differ in sign, and both are at or above 0 here
-    if (sample_off[i + 1] < sample_off[i]) return {LOCATE_OFF_ORDER, i + 1, sample_off[i + 1]};
-    const int64_t q = sample_off[i + 1] - sample_off[i];
+    if (off[i + 1] < off[i]) return {LOCATE_OFF_ORDER, i + 1, off[i + 1]};
+    const int64_t q = off[i + 1] - off[i];
     if (q == 0) return {LOCATE_QUERY_EMPTY, i, 0};
-    if (q > LOCATE_MAX_QUERY) return {LOCATE_QUERY_LONG, i, q};
+    if (q > limit) return {LOCATE_QUERY_LONG, i, q};
     if (q > most) most = q;
   }
   *longest = most;

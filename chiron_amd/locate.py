@@ -166,51 +166,42 @@ def events_of(query, window=EVENT_DEFAULTS["window"], threshold=event_threshold(
     return level[:c].copy(), border[:c + 1].copy(), bool(truncated[0])
 
 
-def event_locate_call(queries, ref, penalty=EVENT_DEFAULTS["penalty"], device_id=0):
-    """One chiron_event_locate call.  queries: int16 arrays of 1 .. EVENT_MAX_QUERY event levels; ref: int32 levels or BREAK; penalty:
-    what a skipped column costs, 0 .. EVENT_MAX_PENALTY.  -> int32 [items][blocks][3], as locate_call."""
+def blocks_of_ref(ref_len):
+    return (int(ref_len) + BLOCK - 1) // BLOCK
+
+
+def _dp_call(entry, size, who, what, queries, ref, extra, device_id):
+    """One call of a locate entry point of the library: queries and ref as locate_call takes them, extra the arguments between
+    ref_len and block_out, size the entry's workspace size function, who and what the names _lib.device_workspace reports under."""
     qs = [np.ascontiguousarray(q, dtype=np.int16).reshape(-1) for q in queries]
     level = np.ascontiguousarray(np.concatenate([np.asarray(ref, dtype=np.int32).reshape(-1), np.zeros(1, np.int32)]))
     items, ref_len = len(qs), len(level) - 1
-    event_off = label._offsets([len(q) for q in qs])
-    events = np.ascontiguousarray(np.concatenate(qs + [np.zeros(1, np.int16)]))
+    off = label._offsets([len(q) for q in qs])
+    values = np.ascontiguousarray(np.concatenate(qs + [np.zeros(1, np.int16)]))
     out = np.zeros((items, blocks_of_ref(ref_len), 3), dtype=np.int32)
-    args = (events.ctypes.data, event_off.ctypes.data, items, level.ctypes.data, ref_len, int(penalty), out.ctypes.data if out.size else None)
+    args = (values.ctypes.data, off.ctypes.data, items, level.ctypes.data, ref_len) + tuple(extra) + (out.ctypes.data if out.size else None,)
     if items == 0 or ref_len == 0:                      # nothing to compute: the library checks its arguments and touches no device
-        _lib.check(_lib.load().chiron_event_locate(device_id, *args, None, 0, 0, None))
+        _lib.check(getattr(_lib.load(), entry)(device_id, *args, None, 0, 0, None))
         return out
     import torch  # noqa: F401  before the size function loads the library: torch's ROCm runtime has to come up first (_lib.py)
-    need = workspace_size_events(items, int(event_off[-1]), ref_len)
-    lib, ws, stream = _lib.device_workspace(need, device_id, "locate.event_locate_call", "event locate kernel")
-    _lib.check(lib.chiron_event_locate(device_id, *args, ws.data_ptr(), need, 0, stream))
+    need = size(items, int(off[-1]), ref_len)
+    lib, ws, stream = _lib.device_workspace(need, device_id, who, what)
+    _lib.check(getattr(lib, entry)(device_id, *args, ws.data_ptr(), need, 0, stream))
     del ws
     return out
 
 
-def blocks_of_ref(ref_len):
-    return (int(ref_len) + BLOCK - 1) // BLOCK
+def event_locate_call(queries, ref, penalty=EVENT_DEFAULTS["penalty"], device_id=0):
+    """One chiron_event_locate call.  queries: int16 arrays of 1 .. EVENT_MAX_QUERY event levels; ref: int32 levels or BREAK; penalty:
+    what a skipped column costs, 0 .. EVENT_MAX_PENALTY.  -> int32 [items][blocks][3], as locate_call."""
+    return _dp_call("chiron_event_locate", workspace_size_events, "locate.event_locate_call", "event locate kernel", queries, ref, (int(penalty),), device_id)
 
 
 def locate_call(queries, ref, device_id=0):
     """One chiron_signal_locate call.  queries: int16 arrays of 1 .. MAX_QUERY samples; ref: int32 levels or BREAK.
     -> int32 [items][blocks][3]: per block of BLOCK columns the least cost of a path that ends in it, the smallest column where one
     ends, and the smallest column where such a path starts; NONE in all three for a block without a path."""
-    qs = [np.ascontiguousarray(q, dtype=np.int16).reshape(-1) for q in queries]
-    level = np.ascontiguousarray(np.concatenate([np.asarray(ref, dtype=np.int32).reshape(-1), np.zeros(1, np.int32)]))
-    items, ref_len = len(qs), len(level) - 1
-    sample_off = label._offsets([len(q) for q in qs])
-    samples = np.ascontiguousarray(np.concatenate(qs + [np.zeros(1, np.int16)]))
-    out = np.zeros((items, blocks_of_ref(ref_len), 3), dtype=np.int32)
-    args = (samples.ctypes.data, sample_off.ctypes.data, items, level.ctypes.data, ref_len, out.ctypes.data if out.size else None)
-    if items == 0 or ref_len == 0:                      # nothing to compute: the library checks its arguments and touches no device
-        _lib.check(_lib.load().chiron_signal_locate(device_id, *args, None, 0, 0, None))
-        return out
-    import torch  # noqa: F401  before the size function loads the library: torch's ROCm runtime has to come up first (_lib.py)
-    need = workspace_size(items, int(sample_off[-1]), ref_len)
-    lib, ws, stream = _lib.device_workspace(need, device_id, "locate.locate_call", "locate kernel")
-    _lib.check(lib.chiron_signal_locate(device_id, *args, ws.data_ptr(), need, 0, stream))
-    del ws
-    return out
+    return _dp_call("chiron_signal_locate", workspace_size, "locate.locate_call", "locate kernel", queries, ref, (), device_id)
 
 
 def summarise(blocks, q_len):

@@ -53,36 +53,36 @@ int main() {
       if (q > want_longest) want_longest = q;
     }
     int64_t longest = -1;
-    LocateFinding f = event_check_offsets(off, items, limit, &longest);
+    LocateFinding f = locate_check_offsets(off, items, limit, &longest);
     CHECK(f.fault == LOCATE_FINE && longest == want_longest);
-    CHECK(event_launches(longest) == (longest + 63) / 64);
+    CHECK(locate_launches(longest) == (longest + 63) / 64);
     if (items > 0) {
       const int64_t keep = off[items];
       off[items] = off[items - 1];
-      f = event_check_offsets(off, items, limit, &longest);
+      f = locate_check_offsets(off, items, limit, &longest);
       CHECK(f.fault == LOCATE_QUERY_EMPTY && f.at == items - 1);
       off[items] = off[items - 1] - 1;
-      f = event_check_offsets(off, items, limit, &longest);
+      f = locate_check_offsets(off, items, limit, &longest);
       CHECK(f.fault == LOCATE_OFF_ORDER && f.at == items && f.value == off[items - 1] - 1);
       off[items] = off[items - 1] + limit + 1;
-      f = event_check_offsets(off, items, limit, &longest);
+      f = locate_check_offsets(off, items, limit, &longest);
       CHECK(f.fault == LOCATE_QUERY_LONG && f.at == items - 1 && f.value == limit + 1);
       off[items] = INT64_MAX;   // the difference stays inside int64: both offsets are at or above 0
-      f = event_check_offsets(off, items, limit, &longest);
+      f = locate_check_offsets(off, items, limit, &longest);
       CHECK(f.fault == LOCATE_QUERY_LONG && f.at == items - 1);
       off[items] = keep;
-      CHECK(event_check_offsets(off, items, limit, &longest).fault == LOCATE_FINE);
+      CHECK(locate_check_offsets(off, items, limit, &longest).fault == LOCATE_FINE);
     }
     const int64_t keep0 = off[0];
     off[0] = -1;
-    f = event_check_offsets(off, items, limit, &longest);
+    f = locate_check_offsets(off, items, limit, &longest);
     CHECK(f.fault == LOCATE_OFF_NEGATIVE && f.at == 0 && f.value == -1);
     off[0] = INT64_MIN;
-    CHECK(event_check_offsets(off, items, limit, &longest).fault == LOCATE_OFF_NEGATIVE);
+    CHECK(locate_check_offsets(off, items, limit, &longest).fault == LOCATE_OFF_NEGATIVE);
     off[0] = keep0;
     free(off);
   }
-  CHECK(event_launches(1) == 1 && event_launches(64) == 1 && event_launches(65) == 2 && event_launches(EVENT_MAX_QUERY) == 128);
+  CHECK(locate_launches(1) == 1 && locate_launches(64) == 1 && locate_launches(65) == 2 && locate_launches(EVENT_MAX_QUERY) == 128);
   CHECK(event_level(7, 2) == 4 && event_level(-7, 2) == -3 && event_level(-8, 2) == -4 && event_level(-1, 2) == 0 && event_level(-3, 2) == -1 &&
         event_level(0, 5) == 0 && event_level(32767 * 9ll, 9) == 32767 && event_level(-32768 * 9ll, 9) == -32768);
 

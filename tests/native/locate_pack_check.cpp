@@ -43,32 +43,32 @@ int main() {
       if (q > want_longest) want_longest = q;
     }
     int64_t longest = -1;
-    LocateFinding f = locate_check_offsets(off, items, &longest);
+    LocateFinding f = locate_check_offsets(off, items, LOCATE_MAX_QUERY, &longest);
     CHECK(f.fault == LOCATE_FINE && longest == want_longest);
     CHECK(locate_launches(longest) == (longest + 63) / 64);
     if (items > 0) {   // one fault of each kind at the last query: found there, and nothing past the array is touched
       const int64_t keep = off[items];
       off[items] = off[items - 1];
-      f = locate_check_offsets(off, items, &longest);
+      f = locate_check_offsets(off, items, LOCATE_MAX_QUERY, &longest);
       CHECK(f.fault == LOCATE_QUERY_EMPTY && f.at == items - 1);
       off[items] = off[items - 1] - 1;
-      f = locate_check_offsets(off, items, &longest);
+      f = locate_check_offsets(off, items, LOCATE_MAX_QUERY, &longest);
       CHECK(f.fault == LOCATE_OFF_ORDER && f.at == items && f.value == off[items - 1] - 1);
       off[items] = off[items - 1] + LOCATE_MAX_QUERY + 1;
-      f = locate_check_offsets(off, items, &longest);
+      f = locate_check_offsets(off, items, LOCATE_MAX_QUERY, &longest);
       CHECK(f.fault == LOCATE_QUERY_LONG && f.at == items - 1 && f.value == LOCATE_MAX_QUERY + 1);
       off[items] = INT64_MAX;   // the difference stays inside int64: both offsets are at or above 0
-      f = locate_check_offsets(off, items, &longest);
+      f = locate_check_offsets(off, items, LOCATE_MAX_QUERY, &longest);
       CHECK(f.fault == LOCATE_QUERY_LONG && f.at == items - 1);
       off[items] = keep;
-      CHECK(locate_check_offsets(off, items, &longest).fault == LOCATE_FINE);
+      CHECK(locate_check_offsets(off, items, LOCATE_MAX_QUERY, &longest).fault == LOCATE_FINE);
     }
     const int64_t keep0 = off[0];
     off[0] = -1;
-    f = locate_check_offsets(off, items, &longest);
+    f = locate_check_offsets(off, items, LOCATE_MAX_QUERY, &longest);
     CHECK(f.fault == LOCATE_OFF_NEGATIVE && f.at == 0 && f.value == -1);   // reported before anything behind it is looked at
     off[0] = INT64_MIN;
-    CHECK(locate_check_offsets(off, items, &longest).fault == LOCATE_OFF_NEGATIVE);
+    CHECK(locate_check_offsets(off, items, LOCATE_MAX_QUERY, &longest).fault == LOCATE_OFF_NEGATIVE);
     off[0] = keep0;
     free(off);
   }

@@ -69,6 +69,21 @@ def test_reference_and_query_edges(built, R):
         assert _skips_taken(queries, e, 1) >= 4                                     # the skip is not idle in these cases
 
 
+@pytest.mark.parametrize("R", [17, 1025, 2049])
+def test_the_two_kernels_agree_where_no_skip_can_pay(built, R):
+    """event_locate_kernel and locate_kernel are one sweep at two reaches (csrc/locate_sweep.h); this holds them to each other.  P =
+    65534, levels and queries within +-300 and Q <= 100: a path without a skip to any column costs at most 100 x 600 < P, so no
+    cheapest path holds a skip and chiron_event_locate gives chiron_signal_locate's triples, every one.  At P = 0 it does not."""
+    rng = np.random.default_rng(7700 + R)
+    for breaks in (0.0, 0.1):
+        e = cases.random_reference(rng, R, breaks)
+        queries = [cases.random_query(rng, Q) for Q in (1, C - 1, C, C + 1, 100)]
+        assert all(len(q) * 600 < 65534 for q in queries)
+        by_samples = locate.locate_call(queries, e)
+        assert np.array_equal(locate.event_locate_call(queries, e, 65534), by_samples)
+        assert not np.array_equal(locate.event_locate_call(queries, e, 0), by_samples)
+
+
 def _path_query(e, cols):
     return e[np.asarray(cols)].astype(np.int16)
 
