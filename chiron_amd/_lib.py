@@ -28,6 +28,7 @@ CTC_WANT_GRAD, CTC_TRUSTED = 1, 2
 CTC_MAX_T, CTC_MAX_LABEL = 8192, 1 << 24
 ALIGN_MAX_LEN, ALIGN_BAND0, ALIGN_THREADS, ALIGN_LDS_SLOTS, ALIGN_MAX_GROUPS = 1 << 17, 256, 256, 4096, 2048
 INFIX_MAX_READ, INFIX_MAX_WINDOW, INFIX_BAND0, INFIX_THREADS, INFIX_LDS_SLOTS, INFIX_MAX_GROUPS = 1 << 17, (1 << 20) - 1, 256, 256, 4096, 2048
+OVERLAP_MAX_READ = 1 << 17
 SEED_K, SEED_BIN, SEED_THREADS, SEED_MAX_GROUPS, SEED_MAX_GENOME = 15, 256, 256, 2048, (1 << 31) - (1 << 18)
 SEED_MAX_CANDIDATES = 8
 LABEL_MAX_FRAMES, LABEL_MAX_BASES, LABEL_THREADS, LABEL_LDS_SLOTS, LABEL_MAX_GROUPS = 1 << 24, 1 << 22, 256, 4096, 1024
@@ -164,6 +165,9 @@ SYMBOLS = [
     ("chiron_align_infix_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     ("chiron_align_infix", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("chiron_align_overlap_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    ("chiron_align_overlap", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     ("chiron_seed_workspace_size", C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     ("chiron_seed_reads", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -360,6 +360,24 @@ int launch_align(const AlignParams& p, int groups, hipStream_t stream);  // 0 on
 int launch_infix(const AlignParams& p, int groups, hipStream_t stream);  // 0 on success
 
 // ---------------------------------------------------------------------------------------------
+// Read-to-read overlaps (overlap.hip): dovetail alignment inside the caller's band of diagonals, the same sweep under another
+// cell policy; the reads are packed once and a pair names two of them
+// ---------------------------------------------------------------------------------------------
+struct OverlapPair {
+  int64_t a, b;              // the first code of read a and of read b in `codes`
+  int32_t n, m;              // their lengths
+  int32_t dlo, dhi;          // the band, clipped to -n .. m and not empty
+};
+struct OverlapParams {
+  const uint8_t* codes;      // the call's reads, one after the other (0..3 bases, 4 matches nothing)
+  const OverlapPair* pair;   // [pairs]
+  int64_t pairs;
+  int64_t* rows;             // [groups][row_slots] cells of bands wider than CHIRON_ALIGN_LDS_SLOTS, or null when none is
+  int64_t row_slots;         // the widest band of the call, in diagonals
+  int32_t* out;              // [pairs][5] cost, M, s, e, status (0, or 1 for a band that fits neither row: all four are 0 then)
+};
+
+// ---------------------------------------------------------------------------------------------
 // CTC forced alignment (ctc_align.hip): banded max-plus recursion with traceback, one workgroup per read
 // ---------------------------------------------------------------------------------------------
 struct LabelRead {

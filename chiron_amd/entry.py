@@ -221,6 +221,21 @@ def assess(args):
     return report
 
 
+def overlap(args):
+    """Read-to-read overlaps without a genome: overlap.overlap_command (k-mer votes of every read against the later ones on the
+    host, exact banded dovetail alignment of every candidate pair on the GPU).  Writes <out>/overlaps.paf and
+    <out>/overlap_report.json."""
+    from . import overlap as overlap_mod
+    report = overlap_mod.overlap_command(args.input, args.output, min_votes=args.min_votes, max_occ=args.max_occ, max_overlaps=args.max_overlaps,
+                                         band=args.band, min_overlap=args.min_overlap, min_identity=args.min_identity,
+                                         workspace_mb=args.workspace_mb, device_id=args.device)
+    print("overlap: %d reads, %d candidate pairs; %d overlaps kept (%s); dropped: %d short, %d below the identity, %d at a band edge"
+          % (report["reads"], report["candidate_pairs"], report["kept"]["total"],
+             ", ".join("%d %s" % (report["kept"][t], t) for t in overlap_mod.TYPES), report["dropped"]["short"], report["dropped"]["identity"],
+             report["edge"]))
+    return report
+
+
 def map_reads(args):
     """Place called reads in a genome: map.map_command (k-mer votes and exact infix alignment, both on the GPU).  Writes
     <out>/reference/<read>_ref.fasta (what `assess -r` and `label -r` take), <out>/mapped.paf and <out>/map_report.json; exits
@@ -581,6 +596,24 @@ def build_parser():
                          "tag and mapped.sam is written.")
     mp.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
     mp.set_defaults(func=map_reads)
+    ov = subparsers.add_parser("overlap", description="Read-to-read overlaps without a genome: every read votes with its k-mers against the "
+                               "later reads, and every candidate pair is aligned on the GPU by an exact banded dovetail alignment (a suffix "
+                               "of one read against a prefix of the other, containment included).  The defaults are not tuned on real reads.",
+                               help="All-against-all overlaps of called reads: overlaps.paf and a report.")
+    ov.add_argument("-i", "--input", required=True, help="Output folder of `call` (its result/ is read), or a fasta/fastq file or folder.")
+    ov.add_argument("-o", "--output", required=True, help="Folder overlaps.paf and overlap_report.json are written to.")
+    ov.add_argument("--min-votes", dest="min_votes", type=int, default=4, help="Fewest seed votes a pair of reads needs to be aligned at all.")
+    ov.add_argument("--max-occ", dest="max_occ", type=int, default=64, help="K-mers that occur more often in the reads are not indexed.")
+    ov.add_argument("--max-overlaps", dest="max_overlaps", type=int, default=128,
+                    help="Most candidates a read keeps against the reads after it, the highest votes first.")
+    ov.add_argument("--band", type=int, default=256,
+                    help="Half-width of the alignment band around the seeded diagonal.  The band is part of the result's definition: an "
+                         "overlap on a diagonal outside it is not seen; a result on a band edge doubles the band, at most three times.")
+    ov.add_argument("--min-overlap", dest="min_overlap", type=int, default=500, help="Shortest overlap that is kept, in bases of the shorter span.")
+    ov.add_argument("--min-identity", dest="min_identity", type=float, default=0.7, help="Lowest identity M / (M + E) that is kept.")
+    ov.add_argument("--workspace-mb", dest="workspace_mb", type=int, default=4096, help="Device workspace of one alignment call, MiB.")
+    ov.add_argument("--device", type=int, default=0, help="HIP device ordinal.")
+    ov.set_defaults(func=overlap)
     pu = subparsers.add_parser("pileup", description="Consensus and variants from mapped reads: the alignment columns of mapped.sam summed "
                                "per genome position and called on the GPU",
                                help="Pile mapped reads up on the genome: consensus sequence, variants, report.")

@@ -414,7 +414,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *
  * Caller's memory.  This holds for every call below that takes a workspace, a tape or a device output buffer from its caller --
  * chiron_ctc_loss, chiron_rnn_train_forward / _backward, chiron_cnn_train_forward / _backward, chiron_align_pairs,
- * chiron_align_trace, chiron_align_infix, chiron_seed_reads, chiron_seed_candidates, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
+ * chiron_align_trace, chiron_align_infix, chiron_align_overlap, chiron_seed_reads, chiron_seed_candidates, chiron_ctc_align, chiron_ctc_score, chiron_demux_windows,
  * chiron_pileup, chiron_signal_levels, chiron_signal_refine, chiron_signal_locate, chiron_event_locate and chiron_signal_score; their own comments say "uninitialised" or name the size function and mean this:
  *   - workspace, tape and output buffers may hold anything on entry: the results do not depend on it (the library clears what it
  *     needs cleared, on the call's stream);
@@ -425,7 +425,7 @@ chiron_status chiron_device_pci_bus_id(int32_t device_id, char* out, size_t cap)
  *     extents, is read or written: a caller may pack other data right behind a workspace of exactly that size.
  * tests/test_gpu_workspace.py holds every one of these calls to the three parts (chiron_signal_levels: tests/test_gpu_squiggle.py; chiron_signal_refine:
  * tests/test_gpu_refine.py; chiron_signal_locate: tests/test_gpu_locate.py; chiron_event_locate: tests/test_gpu_event_locate.py;
- * chiron_signal_score: tests/test_gpu_modcall.py). */
+ * chiron_signal_score: tests/test_gpu_modcall.py; chiron_align_overlap: tests/test_gpu_overlap.py). */
 #define CHIRON_CTC_WANT_GRAD 1u
 #define CHIRON_CTC_TRUSTED 2u   /* chiron_ctc_loss: the caller has checked seq_len / labels / label_len: no read-back, no sync */
 #define CHIRON_CTC_MAX_T 8192
@@ -665,6 +665,57 @@ chiron_status chiron_align_infix_workspace_size(int64_t pairs, int64_t max_read,
 chiron_status chiron_align_infix(int32_t device_id, const uint8_t* codes, const int64_t* read_off, const int64_t* win_off, int64_t pairs,
                                  int32_t band0, uint32_t flags, int32_t* edit_out, int32_t* match_out, int32_t* start_out,
                                  int32_t* end_out, int32_t* band_out, void* workspace, void* stream);
+
+/* Read-to-read overlaps: dovetail alignment of two reads -- a suffix of one against a prefix of the other, containment as the
+ * limiting case -- inside a band of diagonals the caller gives.  Same codes as chiron_align_pairs (4 matches nothing).
+ *
+ * Read a has n bases and read b has m.  A path runs through the (n+1) x (m+1) table by diagonal, down and right moves; it STARTS on
+ * row 0 or on column 0 and ENDS on row n or on column m, and every cell of it lies on a diagonal d = j - i of [dlo, dhi].  Its
+ * cost is 2 E - M: M counts the diagonal moves on equal codes below 4, E every other move.  (Under unit cost the empty overlap
+ * would always win; the score M - 2 E rises along any stretch of identity above 2/3.)  A boundary cell is named by its diagonal
+ * shifted by n: a start (0, j) is s = j + n and a start (i, 0) is s = n - i; an end (n, j) is e = j and an end (i, m) is
+ * e = m - i + n; a corner has one value either way.  The result of a pair is the tuple (cost, M, s, e) that is smallest in this
+ * order over all paths in the band: smallest cost, then largest M, then smallest s, then smallest e.  It is a property of the
+ * inputs, not of a tie order inside the kernel, and E = (cost + M) / 2.
+ *
+ * THE BAND IS PART OF THE DEFINITION, not an accelerator with a certificate as in chiron_align_pairs and chiron_align_infix: an
+ * overlap on a diagonal outside it (a repeat) is another path, which nothing computed inside the band can exclude.  The kernel
+ * never widens; chiron_amd/overlap.py owns the rule that does.  The band is clipped to the table's diagonals [-n, m] first, which
+ * then always holds a boundary start; a band that is empty after clipping is refused.  The empty path at a corner, (0, m) on
+ * diagonal m or (n, 0) on diagonal -n, costs 0, so the cost is never positive while the band holds one of those two diagonals; a
+ * band that holds neither has no empty path (for n, m > 0) and its cost may be positive.  n = 0 or m = 0 gives cost 0 and M 0 at
+ * the smallest s (= e) of the band.
+ *
+ * One workgroup of CHIRON_ALIGN_THREADS threads aligns one pair, pair p on workgroup p mod the group count (at most
+ * CHIRON_ALIGN_MAX_GROUPS), by the banded anti-diagonal sweep of chiron_align_pairs under another cell policy; a cell carries
+ * (cost, -M, start) in one signed 64-bit key cost * 2^40 - M * 2^20 + (start diagonal + 2^17), exact while a read has at most
+ * CHIRON_OVERLAP_MAX_READ bases: M and the biased start stay below 2^20 and |cost| below 2^20.  The result is exact,
+ * deterministic, and independent of what else is in the call.
+ *
+ * Workspace (device memory), each part rounded up to 256 bytes: 32 bytes and five int32 a pair, total_bases bytes of codes, and --
+ * when max_band, the widest clipped band of the call in diagonals, is above the CHIRON_ALIGN_LDS_SLOTS the kernel keeps on chip --
+ * one row of max_band 64-bit cells for each of min(pairs, CHIRON_ALIGN_MAX_GROUPS) workgroups.  Larger values of any argument
+ * are fine.  Host-only.  CHIRON_ERR_INVALID: a negative argument.  CHIRON_ERR_OVERFLOW: pairs or reads > 2^24, total_bases >
+ * reads * CHIRON_OVERLAP_MAX_READ, max_band > 2 * CHIRON_OVERLAP_MAX_READ + 1; within those bounds every offset the kernel forms
+ * is 64-bit.                                                                                                                     */
+#define CHIRON_OVERLAP_MAX_READ (1 << 17)
+chiron_status chiron_align_overlap_workspace_size(int64_t reads, int64_t total_bases, int64_t pairs, int64_t max_band, size_t* bytes);
+
+/* Align `pairs` pairs of the call's `reads` reads in one launch.  codes: HOST bytes; read r is codes[read_off[r] .. read_off[r+1]);
+ * read_off is HOST int64 [reads + 1], non-negative and non-decreasing; the reads are copied once however many pairs name them.
+ * pair_a, pair_b (read indices), dlo, dhi: HOST int32 [pairs]; pair p aligns read pair_a[p] as a against read pair_b[p] as b on
+ * the diagonals dlo[p] .. dhi[p], both ends included, clipped to the table.  out: HOST int32 [pairs][5]: cost, M, s, e and a
+ * status that is 0 in every result this call returns.  workspace: device memory on device_id of at least the size function's
+ * bytes for (reads, read_off[reads] - read_off[0], pairs, the widest clipped band) ("Caller's memory" above); workspace_bytes says
+ * how many it has.  flags: 0 (reserved).  Runs overlap_kernel on `stream` (a hipStream_t; NULL = the null stream) and synchronises
+ * it before returning.  CHIRON_ERR_INVALID: unknown flags, a negative count, a null array that is needed, a negative or
+ * decreasing offset, a code above 4, a read index outside 0 .. reads - 1, a band that is empty after clipping, a workspace smaller
+ * than needed.  CHIRON_ERR_OVERFLOW: a read above CHIRON_OVERLAP_MAX_READ bases (the key's limit), pairs or reads > 2^24.  All of
+ * it before anything is copied or launched, and `out` is written only by a call that returns CHIRON_OK.  pairs == 0 touches no
+ * device and writes nothing.                                                                                                     */
+chiron_status chiron_align_overlap(int32_t device_id, const uint8_t* codes, const int64_t* read_off, int64_t reads, const int32_t* pair_a,
+                                   const int32_t* pair_b, const int32_t* dlo, const int32_t* dhi, int64_t pairs, int32_t* out,
+                                   void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
 
 /* Seeding of the read mapper: where in a genome each read probably lies, from k-mer votes.  The index is the genome's k-mers of
  * k = CHIRON_SEED_K bases, 2 bits a base with the first base highest, sorted by value: idx_val[i] the value, idx_pos[i] the
