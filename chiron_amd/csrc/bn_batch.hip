@@ -9,6 +9,8 @@ namespace chiron {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Both kernels give a block 256 / (C / 4) whole rows per iteration, one float4 channel group per thread: C <= BN_BATCH_MAX_C
+// (kernels.h; above it a block holds no whole row and the row loops would not advance -- chiron_engine_plan refuses such a model).
 // sums[c] += sum_m x[m][c], sums[C + c] += sum_m x[m][c]^2 (double: 440 000 terms per channel at the bench size)
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, long M, int C, double* __restrict__ sums) {
   __shared__ double red[2][256][4];
@@ -17,7 +19,8 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
   const int rsub = threadIdx.x / c4n;       // row sub-index inside the block
   const int rper = blockDim.x / c4n;        // rows per block iteration
   double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
-  for (long m = (long)blockIdx.x * rper + rsub; m < M; m += (long)gridDim.x * rper) {
+  // threads past the last whole row of the block (256 % c4n of them) stay idle: their row belongs to the next block
+  for (long m = (long)blockIdx.x * rper + rsub; rsub < rper && m < M; m += (long)gridDim.x * rper) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(x + m * C + cg * 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -63,6 +66,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(float* __restrict__ x, co
   const int cg = threadIdx.x % c4n;
   const int rsub = threadIdx.x / c4n;
   const int rper = blockDim.x / c4n;
+  // Where c4n does not divide 256 (C = 192: c4n 48, rper 5) threads 240 .. 255 have rsub == rper: row blockIdx * rper + rper is the
+  // next block's first row, and transforming it here as well would apply x * inv + sh twice, in place and unordered.
+  if (rsub >= rper) return;
   float inv[4], sh[4], ainv[4] = {1.f, 1.f, 1.f, 1.f}, ash[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int j = 0; j < 4; ++j) {

@@ -288,6 +288,14 @@ static chiron_status plan_sizes(const chiron_model_desc* d, const chiron_engine_
   if (o->dtype != CHIRON_F32 && o->dtype != CHIRON_F16 && o->dtype != CHIRON_F32_SPLIT && o->dtype != CHIRON_F16_W2)
     return fail(CHIRON_ERR_INVALID, "dtype %d unknown (0 = f32, 1 = f16, 2 = f32 as hi/lo half pairs, 3 = f16 activations against hi/lo weights)", o->dtype);
   if (o->max_beam < 0) return fail(CHIRON_ERR_INVALID, "max_beam %d", o->max_beam);
+  if (o->max_beam > 0 && d->classes != CHIRON_CLASSES)
+    return fail(CHIRON_ERR_INVALID, "max_beam %d with classes %d: the beam search kernels are built for %d classes (greedy decoding takes 2..%d)",
+                o->max_beam, d->classes, CHIRON_CLASSES, CHIRON_KMAX);
+  if (d->bn_mode == CHIRON_BN_BATCH)
+    for (int i = 0; i < map.n_sites; ++i)
+      if (map.site[i].co > BN_BATCH_MAX_C)
+        return fail(CHIRON_ERR_INVALID, "bn_mode=batch: a convolution with %d output channels; the batch-statistics kernels cover at most %d",
+                    map.site[i].co, BN_BATCH_MAX_C);
   const bool f16 = o->dtype == CHIRON_F16 || o->dtype == CHIRON_F16_W2, split = o->dtype == CHIRON_F32_SPLIT, bn_batch = d->bn_mode == CHIRON_BN_BATCH;
   const uint64_t B = (uint64_t)o->max_batch, BP = (uint64_t)roundup(o->max_batch, 16), L = (uint64_t)o->segment_len, H = d->hidden, K = d->classes;
   SiteFrames fr[MAX_SITES];
@@ -297,6 +305,7 @@ static chiron_status plan_sizes(const chiron_model_desc* d, const chiron_engine_
     tmax = std::max<uint64_t>(tmax, (uint64_t)std::max(fr[i].tin, fr[i].tout));
     cmax = std::max<uint64_t>(cmax, (uint64_t)map.site[i].co);
   }
+  if (map.has_stem) cmax = std::max<uint64_t>(cmax, (uint64_t)map.site[0].co);   // the stem's output lies in an activation buffer too
   const uint64_t lasth_ld = !split ? 2 * H : d->rnn_kind == CHIRON_RNN_MULTI ? 2 * (uint64_t)roundup(d->hidden, 32) : (uint64_t)roundup(2 * d->hidden, 32);
   const uint64_t act = B * tmax * cmax * (f16 ? 2 : 4), lasth = T * BP * lasth_ld * 4, z = T * BP * 2 * 4 * H * 4;
   if (B * tmax >= (1ull << 31) || T * BP >= (1ull << 31))
@@ -339,6 +348,7 @@ static chiron_status alloc_slot(chiron_engine* e, Slot* s) {
     tmax = std::max<size_t>(tmax, b.t_out);
     cmax = std::max<size_t>(cmax, b.c);
   }
+  if (e->stem_k > 0) cmax = std::max<size_t>(cmax, e->stem_c);   // wider than every block where the blocks narrow (plan_sizes counts it too)
   chiron_status st;
   if ((st = dev_alloc(e, (void**)&s->tile_ctr, 16 * sizeof(unsigned long long), true))) return st;
   if ((st = dev_alloc(e, (void**)&s->sig, B * L * 4, true))) return st;

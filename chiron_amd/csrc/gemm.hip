@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmParams p) {
         axv[i] = p.sig[ok ? ((long)rb[i] * p.L + in_t) : 0];
       } else {
         const long row = sg.time_major ? ((long)in_t * p.BP + rb[i]) : ((long)rb[i] * sg.w_in + in_t);
-        aptr[i] = sg.src + (ok ? row * sg.lda : 0) + sg.col0 + 4 * kq;
+        aptr[i] = sg.src + (ok ? row * sg.lda : 0) + sg.col0;   // the row's first channel: load_chunk adds the channel, inside cin only
       }
     }
   };
@@ -446,7 +446,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmParams p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) ra[i][0] = axv[i];
     } else {
-      const int ko = kin ? kk - 4 * kq : 0;
+      // past the segment's channels (a K tail: cin < kpad) every lane reads the row's first four, which the mask then drops: an
+      // address at channel 4 kq of a row narrower than that lies in the next rows and, for the tensor's last rows, past its end
+      const int ko = kin ? kk : 0;
 #pragma unroll
       for (int i = 0; i < 4; ++i) ra[i] = *reinterpret_cast<const f32x4*>(aptr[i] + ko);
     }

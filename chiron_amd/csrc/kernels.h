@@ -208,6 +208,11 @@ void launch_stem_conv(const float* sig, const float* w, const float* shift, void
 // destination (a 32-element block boundary), so that each direction can be read as a K-segment of its own.
 void launch_split_convert(const float* src, void* dst, long rows, int cols, int ld, int half, int half_dst, hipStream_t stream);
 // res_layer1 conv2a + conv2b as a piecewise-linear table (pwl.hip)
+constexpr int PWL_TP = 32;        // output positions per workgroup
+constexpr int PWL_MAX_BP = 512;   // breakpoints (= channels of conv2a) held in LDS
+constexpr int PWL_MAX_S = 512;    // samples a workgroup looks at: (PWL_TP - 1) * stride + k
+// what the table form covers: the packer (weight_pack.h) builds no table for any other block, which then runs lifted on the GEMM
+inline bool pwl_covers(int channels, int k, int stride) { return channels <= PWL_MAX_BP && (PWL_TP - 1) * stride + k <= PWL_MAX_S && channels % 4 == 0; }
 struct PwlConvParams {
   const float* sig;   // [B][L]
   const float* bp;    // [nbp] breakpoints of relu(s*a[c] + b[c]), ascending
@@ -285,6 +290,7 @@ void launch_path_prob(const PathProbParams& p, hipStream_t stream);
 // ---------------------------------------------------------------------------------------------
 // batch-statistics BatchNorm (bn_batch.hip): cnn.py:166-188 simple_global_bn
 // ---------------------------------------------------------------------------------------------
+constexpr int BN_BATCH_MAX_C = 1024;   // channels of a batch-BN site: one float4 channel group per thread of a 256-thread block
 void launch_bn_stats(const float* x, long M, int C, double* sums /* [2][C] */, hipStream_t stream);
 // sums[c] += sum_m x[m * ld + col0 + c] over `rows` rows of halves (BP > 0: time-major rows m = t * BP + b, only b < B count)
 void launch_colsum_f16(const void* x, long rows, int ld, int col0, int cin, int BP, int B, double* sums /* [cin], zeroed by the caller */, hipStream_t stream);

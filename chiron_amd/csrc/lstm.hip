@@ -433,7 +433,9 @@ __global__ __launch_bounds__(64 * LSTM_NW, 4) void lstm16_kernel(const LstmParam
 template <int FMT>  // 0 fp32, 1 halves, 2 split hi/lo
 __global__ __launch_bounds__(256) void lift_kernel(const float* __restrict__ sig, const float* __restrict__ a, const float* __restrict__ b,
                                                    void* __restrict__ outv, long n_pos, int C) {
-  const int c8 = C / 8;  // 8 channels per thread
+  // 8 channels per thread; fp32 takes any multiple of 4 (the last thread of a row then stores four: a and b are padded to 32 channels,
+  // weight_pack.h lift_a), the half formats only see multiples of 64
+  const int c8 = (C + 7) / 8;
   const long total = n_pos * c8;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long pos = i / c8;
@@ -445,7 +447,7 @@ __global__ __launch_bounds__(256) void lift_kernel(const float* __restrict__ sig
     if (FMT == 0) {
       float* o = reinterpret_cast<float*>(outv) + pos * C + c0;
       *reinterpret_cast<f32x4*>(o) = (f32x4){y[0], y[1], y[2], y[3]};
-      *reinterpret_cast<f32x4*>(o + 4) = (f32x4){y[4], y[5], y[6], y[7]};
+      if (c0 + 4 < C) *reinterpret_cast<f32x4*>(o + 4) = (f32x4){y[4], y[5], y[6], y[7]};
     } else {
       f16x8 v, lo;
 #pragma unroll

@@ -17,10 +17,6 @@ namespace chiron {
 
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-constexpr int PWL_TP = 32;        // output positions per workgroup
-constexpr int PWL_MAX_BP = 512;   // breakpoints (= channels of conv2a) held in LDS
-constexpr int PWL_MAX_S = 512;    // samples a workgroup looks at: (PWL_TP - 1) * stride + k
-
 template <int FMT>
 __global__ __launch_bounds__(256) void pwl_conv_kernel(const PwlConvParams p) {
   __builtin_amdgcn_s_setprio(3);   // a short kernel between the other batches' persistent GEMM waves

@@ -434,7 +434,7 @@ struct WeightPacker {
           ra[c] = W1[c] * f1.inv[c];
           rb[c] = f16 ? 0.f : f1.sh[c];   // the f16 engines keep round 4's arithmetic (shift folded): halves' rounding dominates there
         }
-        if (!batch && !sw.no_pwl) {
+        if (!batch && !sw.no_pwl && pwl_covers(co, b.k, b.stride)) {
           // f[tap][n](s) = sum_c W2b'[tap][c][n] * relu(s*a[c] + b[c]) is piecewise linear in the signal value s:
           // tabulate (alpha, beta) per interval between consecutive breakpoints -b[c]/a[c] (pwl.hip).  float64 sums.
           std::vector<std::pair<double, int>> brk;  // (breakpoint, channel)
@@ -605,6 +605,20 @@ inline chiron_status pack_weights(const chiron_model_desc& d, const BlobMap& map
       if (d.blocks[bi].out_channels % GEMM_BN || (d.blocks[bi].in_channels != 1 && d.blocks[bi].in_channels % 64))
         return set_error(CHIRON_ERR_INVALID, "dtype f16: block %d has %d -> %d channels; the f16 kernels need multiples of 64 / 128", bi,
                          d.blocks[bi].in_channels, d.blocks[bi].out_channels);
+    // the convolution forms of the DMA GEMM exist for K-segments of 256 channels only in these dtypes (gemm.hip launch_dma): any other
+    // width would pack and then find no kernel at the first batch
+    for (int bi = 0; bi < d.n_blocks; ++bi)
+      if (d.blocks[bi].out_channels != 256 || (d.blocks[bi].in_channels != 1 && d.blocks[bi].in_channels != 256))
+        return set_error(CHIRON_ERR_INVALID, "dtype %s: block %d has %d -> %d channels; its convolution kernels are built for 1 -> 256 and 256 -> 256",
+                         split ? "f32-split" : "f16", bi, d.blocks[bi].in_channels, d.blocks[bi].out_channels);
+    // fp16-w2 runs every K-segment twice (hi and lo weight columns): a conv2b on the GEMM has 2 k segments of the GEMM_MAX_SEG
+    for (int bi = 0; bi < d.n_blocks; ++bi) {
+      const chiron_res_block& b = d.blocks[bi];
+      const bool table = b.in_channels == 1 && !sw.no_pwl && pwl_covers(b.out_channels, b.k, b.stride);   // conv2b without a GEMM
+      if (w2 && !table && 2 * b.k > GEMM_MAX_SEG)
+        return set_error(CHIRON_ERR_INVALID, "dtype f16-w2: block %d: conv2b width %d unsupported (1..%d: hi and lo weights take two K-segments per tap)",
+                         bi, b.k, GEMM_MAX_SEG / 2);
+    }
   }
   WeightPacker p{d, map, w, sw, f16, w2, split, batch, f16 ? 2 * GEMM_BK : GEMM_BK, out, ups};
   p.stem_and_blocks(segment_len);

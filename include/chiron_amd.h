@@ -59,7 +59,19 @@ typedef enum {
 } chiron_bn_mode;
 
 /* Topology descriptor: what chiron_model.read_config (chiron_model.py:37-48)
- * plus the checkpoint's variable shapes determine.                           */
+ * plus the checkpoint's variable shapes determine.
+ *
+ * What is accepted (every refusal is CHIRON_ERR_INVALID with its reason, from chiron_engine_plan or chiron_engine_create before any
+ * kernel runs; tests/topology_cases.py runs or pins every line):
+ *   blocks       1 .. CHIRON_MAX_BLOCKS; in_channels = the previous block's out_channels (the stem's, or 1, for the first);
+ *                out_channels any multiple of 4; k 1 .. 16; stride >= 1; i_bn on any block
+ *   stem         k 0 (none) .. 64, stride >= 1, channels any multiple of 8
+ *   recurrence   either kind, 1 .. 8 layers, hidden 100 (the descriptor of the training seams takes no other either)
+ *   classes      2 .. 5 for greedy decoding; max_beam > 0 needs 5
+ *   bn_mode      CHIRON_BN_BATCH: CHIRON_F32 only, and at most 1024 output channels in any convolution
+ *   dtype        CHIRON_F32: all of the above.  CHIRON_F16, CHIRON_F16_W2, CHIRON_F32_SPLIT: blocks of 1 -> 256 and 256 -> 256 channels
+ *                only (a stem, if any, of 256); CHIRON_F16_W2 with a conv2b wider than 8 only on the first block of a model without
+ *                a stem, where it runs as a table                                                                            */
 typedef struct {
   int32_t n_blocks;
   chiron_res_block blocks[CHIRON_MAX_BLOCKS];
